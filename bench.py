@@ -6,6 +6,12 @@ Usage (driver contract):
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N \
         --master-addr 127.0.0.1 bench.py --gpus N ...      # N GPUs, RCCL
 
+A plain run sets up, warms up, times the K steps and prints the result
+line.  --full adds the legs that take runs of their own (today: the
+host-core `cpu_baseline`).  --dump-outputs DIR writes what the last
+timed step returned (a fixed seeded sample of y = Op x and z = Op^H y)
+as DIR/<name>.npy, so two builds can be compared output for output.
+
 Workload:
   N=1  -> BASELINE.json configs[1]: dims (2048,2048,128) fp64 (4.29 GB).
   N>1  -> weak scaling toward the north-star config: dims
@@ -187,6 +193,30 @@ def cpu_baseline(dims):
     }
 
 
+DUMP_MAX_ELEMS = 1 << 21   # per array over all ranks: 16 MiB of fp64
+DUMP_SEED = 20240613
+
+
+def dump_outputs(dirpath, arrays, comm):
+    """Write each named local tensor as DIR/<name>.npy (float64; one
+    file per rank, suffixed _rankR, at world > 1).  An array larger than
+    the budget is sampled at fixed positions drawn once from DUMP_SEED,
+    so the same arguments give the same positions in every run and
+    build."""
+    os.makedirs(dirpath, exist_ok=True)
+    budget = max(DUMP_MAX_ELEMS // comm.size, 1)
+    suffix = "" if comm.size == 1 else f"_rank{comm.rank}"
+    for name, t in arrays.items():
+        flat = t.reshape(-1)
+        if flat.numel() > budget:
+            rng = np.random.default_rng(DUMP_SEED)
+            idx = np.sort(rng.integers(0, flat.numel(), size=budget))
+            flat = flat.index_select(
+                0, torch.as_tensor(idx, device=flat.device))
+        out = flat.detach().cpu().numpy().astype(np.float64, copy=False)
+        np.save(os.path.join(dirpath, f"{name}{suffix}.npy"), out)
+
+
 def _smoke_main(args, op, x, comm, n_gpus, dims, wname, rank):
     """--smoke-gloo body: the same step loop / barrier+sync protocol /
     max-over-ranks reduction / JSON emission as the real bench, sized
@@ -196,13 +226,16 @@ def _smoke_main(args, op, x, comm, n_gpus, dims, wname, rank):
         _smoke_fd_pair(op, x, comm)
     comm.barrier()
     t0 = time.perf_counter()
+    z = None
     for _ in range(args.steps):
-        _smoke_fd_pair(op, x, comm)
+        z = _smoke_fd_pair(op, x, comm)
     comm.barrier()
     t1 = time.perf_counter()
     elapsed = torch.tensor([t1 - t0], dtype=torch.float64)
     comm.allreduce_(elapsed, "max")
     t = float(elapsed.item())
+    if args.dump_outputs and z is not None:
+        dump_outputs(args.dump_outputs, {"z": z}, comm)
     if rank == 0:
         print(json.dumps({
             "metric": "MPIFirstDerivative fp64 matvec+rmatvec pairs/sec",
@@ -218,12 +251,29 @@ def _smoke_main(args, op, x, comm, n_gpus, dims, wname, rank):
         }), flush=True)
 
 
+def _teardown(comm):
+    """Leave the process group in order: without this a rank can abort at
+    interpreter exit (its gloo threads are still joinable) after the
+    result line is already out."""
+    import torch.distributed as dist
+    if dist.is_available() and dist.is_initialized():
+        comm.barrier()
+        dist.destroy_process_group()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=50)  # SURVEY 8d: >=50
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--skip-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs that take runs of their own "
+                         "(the host-core cpu_baseline); off by default")
+    ap.add_argument("--skip-cpu-baseline", action="store_true",
+                    help="with --full: leave the cpu_baseline leg out")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as "
+                         "DIR/<name>.npy (fixed seeded sample)")
     ap.add_argument("--smoke-gloo", action="store_true",
                     help="CPU orchestration smoke (tiny dims, torch "
                          "stand-in kernel; NOT a benchmark)")
@@ -256,6 +306,7 @@ def main():
 
     if args.smoke_gloo:
         _smoke_main(args, op, x, comm, n_gpus, dims, wname, rank)
+        _teardown(comm)
         return
 
     for _ in range(args.warmup):
@@ -269,9 +320,10 @@ def main():
     comm.barrier()
     torch.cuda.synchronize(device)
     t0 = time.perf_counter()
+    y = z = None
     for _ in range(args.steps):
         y = op.matvec(x)
-        _ = op.rmatvec(y)
+        z = op.rmatvec(y)
     comm.barrier()
     torch.cuda.synchronize(device)
     t1 = time.perf_counter()
@@ -280,6 +332,11 @@ def main():
     elapsed = torch.tensor([t1 - t0], dtype=torch.float64, device=device)
     comm.allreduce_(elapsed, "max")
     t = float(elapsed.item())
+
+    if args.dump_outputs and z is not None:
+        # y = Op x and z = Op^H y of the last timed step, as returned
+        dump_outputs(args.dump_outputs,
+                     {"y": y.local_array, "z": z.local_array}, comm)
 
     # roofline of the dominant kernel (fd centered3 matvec, op code 4).
     # One event pair brackets one whole matvec: a single launch at
@@ -327,10 +384,12 @@ def main():
                 "frac": (achieved / HBM_PEAK_GBS) if achieved else None,
                 "traffic": traffic,
             },
-            "cpu_baseline": (None if args.skip_cpu_baseline or n_gpus != 1
-                             else cpu_baseline(dims)),
+            "cpu_baseline": (cpu_baseline(dims)
+                             if args.full and not args.skip_cpu_baseline
+                             and n_gpus == 1 else None),
         }
         print(json.dumps(result), flush=True)
+    _teardown(comm)
 
 
 if __name__ == "__main__":

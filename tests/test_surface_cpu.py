@@ -178,21 +178,28 @@ def test_reference_public_surface_complete():
     """Every public name the reference package exports (its __init__
     __all__ lists across pylops_mpi, basicoperators, signalprocessing,
     waveeqprocessing, optimization, proximal, utils) must exist here.
-    The reference tree is only present in the build container; skip on
-    the GPU box."""
+    The names are the committed list
+    tests/golden/reference_public_names.json (every double-quoted
+    identifier in those __init__ files), so the test needs no reference
+    tree; where one is present the list is also checked against it."""
+    import json
     import os
     import re
-    ref = "/root/reference/pylops_mpi"
-    if not os.path.isdir(ref):
-        import pytest
-        pytest.skip("reference tree not present (GPU box)")
-    names = set()
-    for sub in ("", "basicoperators", "signalprocessing",
-                "waveeqprocessing", "optimization", "proximal", "utils"):
-        f = os.path.join(ref, sub, "__init__.py")
-        if os.path.exists(f):
-            names.update(re.findall(r'"([A-Za-z_][A-Za-z0-9_]*)"',
-                                    open(f).read()))
+    from oracle.refrun import REFERENCE_PATH, reference_available
+    here = os.path.dirname(os.path.abspath(__file__))
+    with open(os.path.join(here, "golden",
+                           "reference_public_names.json")) as fh:
+        names = set(json.load(fh))
+    assert len(names) >= 17
+    if reference_available():
+        live = set()
+        for sub in ("", "basicoperators", "signalprocessing",
+                    "waveeqprocessing", "optimization", "proximal", "utils"):
+            f = os.path.join(REFERENCE_PATH, "pylops_mpi", sub, "__init__.py")
+            if os.path.exists(f):
+                live.update(re.findall(r'"([A-Za-z_][A-Za-z0-9_]*)"',
+                                       open(f).read()))
+        assert live == names, "reference_public_names.json is stale"
     import pylops_mpi_amd as pm
     import pylops_mpi_amd.proximal as prox
     import pylops_mpi_amd.proximal.optimization as po
