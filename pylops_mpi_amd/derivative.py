@@ -17,17 +17,15 @@ and SecondDerivative.py, re-designed MI355X-first:
 import numpy as np
 import torch
 
-from . import _ffi
+from . import kernels
 from .distributedarray import (DistributedArray, Partition,
-                               local_split)
+                               as_numpy_dtype, local_split)
 from .linearoperator import MPILinearOperator
 from .rebalance import rebalance_1d
 
 _FD1_OPS = {("forward", 0): (0, 1), ("backward", 0): (2, 3),
             ("centered", 3): (4, 5), ("centered", 5): (6, 7)}
 _FD2_OPS = {"forward": (8, 9), "backward": (10, 11), "centered": (12, 13)}
-_NP_OF = {torch.float64: np.float64, torch.float32: np.float32,
-          torch.complex128: np.complex128, torch.complex64: np.complex64}
 
 # bench instrumentation: when enabled, each stencil kernel launch records a
 # HIP event pair on the launch stream (torch's current stream, which is
@@ -102,7 +100,7 @@ class _FDBase(MPILinearOperator):
         m = int(np.prod(self.dims[1:], initial=1))
         planes = flat.view(nloc, m) if m > 1 else flat.view(nloc, 1)
         x._require_compute()
-        w = int(_ffi.lib().pam_fd_halo_width(op))
+        w = kernels.fd_halo_width(op)
         if comm.size > 1 and w > 0:
             # every rank with a neighbour sends w planes (rank 0 to the
             # next, rank P-1 to the previous), so EVERY rank's block must
@@ -117,23 +115,15 @@ class _FDBase(MPILinearOperator):
         y_out = torch.empty_like(planes)
         y = y_out
         if planes.is_complex():
-            # real-coefficient stencil acts componentwise: run the real
-            # kernels on the interleaved (re,im) view with doubled columns
+            # the halo planes travel as interleaved (re,im) reals with
+            # doubled columns, the layout kernels.fd_apply launches on
             planes = torch.view_as_real(planes).reshape(nloc, 2 * m)
             y = torch.view_as_real(y_out).reshape(nloc, 2 * m)
         row0 = int(np.sum([s[0] for s in shapes[: comm.rank]], initial=0))
-        stream = torch.cuda.current_stream(planes.device).cuda_stream
-        m = planes.shape[1]
-        dt = _ffi.dtype_code(planes.dtype)
-        edge = 1 if self.edge else 0
 
         def launch(gfp, gbp, r0, r1):
-            _ffi.checked(_ffi.lib().pam_fd_apply(
-                stream, op, edge, planes.data_ptr(),
-                gfp.data_ptr() if gfp is not None else None,
-                gbp.data_ptr() if gbp is not None else None,
-                y.data_ptr(), nloc, m, row0, self.dims[0], r0, r1,
-                self._coeff(), dt), "fd_apply")
+            kernels.fd_apply(y, planes, gfp, gbp, op, self.edge, row0,
+                             self.dims[0], r0, r1, self._coeff())
 
         ev = _record_events(op) if KERNEL_TIMING else None
         if ev is not None:
@@ -169,7 +159,7 @@ class _FDBase(MPILinearOperator):
         return DistributedArray(
             int(np.prod(self.dims)), comm, Partition.SCATTER, 0,
             local_array=y_out.view(-1), local_shapes=[(c,) for c in counts],
-            dtype=_NP_OF[y_out.dtype])
+            dtype=as_numpy_dtype(y_out.dtype))
 
     def _matvec(self, x: DistributedArray) -> DistributedArray:
         return self._apply(x, self._op_mv)

@@ -23,7 +23,7 @@ from typing import List, Optional, Tuple, Union
 import numpy as np
 import torch
 
-from . import _ffi
+from . import kernels
 from .comm import PamComm, get_default_comm
 
 _TORCH_DTYPES = {
@@ -39,6 +39,13 @@ def as_torch_dtype(dtype) -> torch.dtype:
     if isinstance(dtype, torch.dtype):
         return dtype
     return _TORCH_DTYPES[np.dtype(dtype)]
+
+
+def as_numpy_dtype(dtype) -> np.dtype:
+    """Inverse of :func:`as_torch_dtype`."""
+    if isinstance(dtype, torch.dtype):
+        return _NP_DTYPES[dtype]
+    return np.dtype(dtype)
 
 
 class Partition(Enum):
@@ -62,9 +69,6 @@ def local_split(global_shape: Tuple, size: int, rank: int,
     return tuple(local_shape)
 
 
-# per-device reduction scratch: (ws, out) float64 tensors
-_red_scratch = {}
-
 # sub-communicator cache: creating a torch process group is collective, so
 # identical masks must map to one group (ref subcomm_split, :74-100)
 _subcomm_cache = {}
@@ -76,17 +80,6 @@ def _get_subcomm(comm, mask_key):
         _subcomm_cache[key] = comm.split_by(list(mask_key),
                                             keys=list(range(comm.size)))
     return _subcomm_cache[key]
-
-
-def _reduce_buffers(device):
-    key = (device.type, device.index)
-    if key not in _red_scratch:
-        n = int(_ffi.lib().pam_reduce_ws_elems())
-        _red_scratch[key] = (
-            torch.empty(2 * n, dtype=torch.float64, device=device),
-            torch.empty(2, dtype=torch.float64, device=device),
-        )
-    return _red_scratch[key]
 
 
 class DistributedArray:
@@ -234,35 +227,10 @@ class DistributedArray:
 
     # --------------------------------------------------------------- helpers
     def _require_compute(self):
-        if self._local_array.device.type != "cuda":
-            raise RuntimeError(
-                "pam: compute ops require a CUDA (MI355X) device tensor — "
-                "there is no CPU compute path")
-        _ffi.lib()  # raises ImportError if the HIP extension is missing
-
-    def _stream(self):
-        return torch.cuda.current_stream(self._local_array.device).cuda_stream
-
-    def _dt(self):
-        return _ffi.dtype_code(self._local_array.dtype)
-
-    def _flat(self) -> torch.Tensor:
-        t = self._local_array
-        return t.reshape(-1) if t.is_contiguous() else t.contiguous().view(-1)
+        kernels.require_device(self._local_array)
 
     def _is_cplx(self) -> bool:
         return self._local_array.is_complex()
-
-    def _ew(self, t: Optional[torch.Tensor] = None):
-        """(flat, count, dtype_code) for element-wise kernels; complex
-        arrays are handled as their 2n-float real view (valid for
-        add/sub/neg/fill and REAL-alpha axpy/xpby/scale)."""
-        t = self._local_array if t is None else t
-        flat = t.reshape(-1) if t.is_contiguous() else t.contiguous().view(-1)
-        if t.is_complex():
-            rv = torch.view_as_real(flat).reshape(-1)
-            return rv, rv.numel(), _ffi.dtype_code(rv.dtype)
-        return flat, flat.numel(), _ffi.dtype_code(t.dtype)
 
     def _like(self, local: Optional[torch.Tensor] = None) -> "DistributedArray":
         return DistributedArray(self._global_shape, self._base_comm,
@@ -452,53 +420,27 @@ class DistributedArray:
 
     # ------------------------------------------------------------- math (HIP)
     def __neg__(self):
-        self._require_compute()
         out = self._like()
-        a, n, dt = self._ew()
-        o, _, _ = self._ew(out._local_array)
-        _ffi.checked(_ffi.lib().pam_neg(
-            self._stream(), o.data_ptr(), a.data_ptr(), n, dt), "neg")
+        kernels.neg(out._local_array, self._local_array)
+        return out
+
+    def _binary(self, kernel, other: "DistributedArray"):
+        self._check_mask(other)
+        self._check_partition_shape(other)
+        out = self._like()
+        kernel(out._local_array, self._local_array, other._local_array)
         return out
 
     def add(self, other: "DistributedArray") -> "DistributedArray":
-        self._check_mask(other)
-        # ref :636-651
-        self._check_partition_shape(other)
-        self._require_compute()
-        out = self._like()
-        a, n, dt = self._ew()
-        b, _, _ = self._ew(other._local_array)
-        o, _, _ = self._ew(out._local_array)
-        _ffi.checked(_ffi.lib().pam_add(
-            self._stream(), o.data_ptr(), a.data_ptr(), b.data_ptr(), n, dt),
-            "add")
-        return out
+        return self._binary(kernels.add, other)  # ref :636-651
 
     def iadd(self, other: "DistributedArray") -> "DistributedArray":
-        self._check_mask(other)
-        # ref :653-659
-        self._check_partition_shape(other)
-        self._require_compute()
-        a, n, dt = self._ew()
-        b, _, _ = self._ew(other._local_array)
-        _ffi.checked(_ffi.lib().pam_axpy(
-            self._stream(), a.data_ptr(), b.data_ptr(), 1.0, n, dt), "iadd")
-        return self
+        return self.iaxpy_(1.0, other)  # ref :653-659
 
     def sub(self, other: "DistributedArray") -> "DistributedArray":
         # bitwise equal to ref __sub__ = add(-other) (ref :624-625),
         # including its mask validation (add() raises on mismatch)
-        self._check_mask(other)
-        self._check_partition_shape(other)
-        self._require_compute()
-        out = self._like()
-        a, n, dt = self._ew()
-        b, _, _ = self._ew(other._local_array)
-        o, _, _ = self._ew(out._local_array)
-        _ffi.checked(_ffi.lib().pam_sub(
-            self._stream(), o.data_ptr(), a.data_ptr(), b.data_ptr(), n, dt),
-            "sub")
-        return out
+        return self._binary(kernels.sub, other)
 
     def multiply(self, x) -> "DistributedArray":
         # ref :661-683
@@ -507,28 +449,13 @@ class DistributedArray:
         if isinstance(x, DistributedArray):
             self._check_partition_shape(x)
             self._check_mask(x)
-            if self._is_cplx():
-                _ffi.checked(_ffi.lib().pam_cmul(
-                    self._stream(), out._flat().data_ptr(),
-                    self._flat().data_ptr(), x._flat().data_ptr(),
-                    self._local_array.numel(), self._dt()), "cmul")
-            else:
-                _ffi.checked(_ffi.lib().pam_mul(
-                    self._stream(), out._flat().data_ptr(),
-                    self._flat().data_ptr(), x._flat().data_ptr(),
-                    self._local_array.numel(), self._dt()), "mul")
+            kernels.mul(out._local_array, self._local_array, x._local_array)
         elif self._is_cplx() and isinstance(x, complex) and x.imag != 0.0:
-            _ffi.checked(_ffi.lib().pam_cscale(
-                self._stream(), out._flat().data_ptr(),
-                self._flat().data_ptr(), float(x.real), float(x.imag),
-                self._local_array.numel(), self._dt()), "cscale")
+            kernels.cscale(out._local_array, self._local_array, x)
         else:
-            # real scalar: componentwise on the (possibly complex) view
-            a, n, dt = self._ew()
-            o, _, _ = self._ew(out._local_array)
-            _ffi.checked(_ffi.lib().pam_scale(
-                self._stream(), o.data_ptr(), a.data_ptr(),
-                float(np.real(x)), n, dt), "scale")
+            # real scalar: componentwise on the (possibly complex) array
+            kernels.scale(out._local_array, self._local_array,
+                          float(np.real(x)))
         return out
 
     # fused solver updates (not in the reference surface — the reference
@@ -540,50 +467,30 @@ class DistributedArray:
         ref cls_basic.py:389-395)."""
         self._check_mask(x)
         self._check_partition_shape(x)
-        self._require_compute()
-        a, n, dt = self._ew()
-        b, _, _ = self._ew(x._local_array)
-        _ffi.checked(_ffi.lib().pam_axpy(
-            self._stream(), a.data_ptr(), b.data_ptr(), float(alpha), n, dt),
-            "axpy")
+        kernels.axpy(self._local_array, x._local_array, alpha)
         return self
 
     def xpby_(self, x: "DistributedArray", beta: float) -> "DistributedArray":
         """self = x + beta * self (REAL beta), fused (CGLS c = r + b*c)."""
         self._check_mask(x)
         self._check_partition_shape(x)
-        self._require_compute()
-        a, n, dt = self._ew()
-        b, _, _ = self._ew(x._local_array)
-        _ffi.checked(_ffi.lib().pam_xpby(
-            self._stream(), a.data_ptr(), b.data_ptr(), float(beta), n, dt),
-            "xpby")
+        kernels.xpby(self._local_array, x._local_array, beta)
         return self
 
     # device-scalar solver fast path: the scalar lives in a caller-owned
-    # 1-element f64 CUDA buffer written by a prior dot_into / pam_scalar_*
+    # 1-element f64 CUDA buffer written by a prior dot_into / scalar_*
     # launch on the same stream, so a CG/CGLS iteration needs one host sync
     # (the stop test) instead of one per dot (see solvers.py).
     def iaxpy_dev_(self, alpha_t: torch.Tensor, x: "DistributedArray",
                    scale: float = 1.0) -> "DistributedArray":
         """self += scale * alpha_t[0] * x (bit-identical to iaxpy_)."""
-        self._require_compute()
-        a, n, dt = self._ew()
-        b, _, _ = self._ew(x._local_array)
-        _ffi.checked(_ffi.lib().pam_axpy_d(
-            self._stream(), a.data_ptr(), b.data_ptr(), alpha_t.data_ptr(),
-            float(scale), n, dt), "axpy_d")
+        kernels.axpy_d(self._local_array, x._local_array, alpha_t, scale)
         return self
 
     def xpby_dev_(self, x: "DistributedArray", beta_t: torch.Tensor,
                   scale: float = 1.0) -> "DistributedArray":
         """self = x + scale * beta_t[0] * self (bit-identical to xpby_)."""
-        self._require_compute()
-        a, n, dt = self._ew()
-        b, _, _ = self._ew(x._local_array)
-        _ffi.checked(_ffi.lib().pam_xpby_d(
-            self._stream(), a.data_ptr(), b.data_ptr(), beta_t.data_ptr(),
-            float(scale), n, dt), "xpby_d")
+        kernels.xpby_d(self._local_array, x._local_array, beta_t, scale)
         return self
 
     def dot_into(self, other: "DistributedArray",
@@ -591,13 +498,7 @@ class DistributedArray:
         """Local dot reduced into ``out_t`` (1-elem f64 device slice); the
         global allreduce is the CALLER's, so the solver can batch several
         dots into one collective.  Real SCATTER arrays only."""
-        self._require_compute()
-        ws, _ = _reduce_buffers(self._local_array.device)
-        _ffi.checked(_ffi.lib().pam_dot(
-            self._stream(), self._flat().data_ptr(), other._flat().data_ptr(),
-            self._local_array.numel(), ws.data_ptr(), out_t.data_ptr(),
-            self._dt()), "dot")
-        return out_t
+        return kernels.dot(self._local_array, other._local_array, out_t)
 
     def __add__(self, x):
         return self.add(x)
@@ -628,30 +529,14 @@ class DistributedArray:
             x = DistributedArray.to_dist(self._local_array, self._base_comm)
             y = DistributedArray.to_dist(other._local_array, self._base_comm)
             return x.dot(y, vdot=vdot)
-        ws, out = _reduce_buffers(self._local_array.device)
         if self._is_cplx():
-            _ffi.checked(_ffi.lib().pam_cdot(
-                self._stream(), self._flat().data_ptr(),
-                other._flat().data_ptr(), self._local_array.numel(),
-                1 if vdot else 0, ws.data_ptr(), out.data_ptr(),
-                self._dt()), "cdot")
+            out = kernels.cdot(self._local_array, other._local_array, vdot)
             self._sub_comm.allreduce_(out, "sum")
             v = out.cpu()
             return np.complex128(complex(float(v[0]), float(v[1])))
-        _ffi.checked(_ffi.lib().pam_dot(
-            self._stream(), self._flat().data_ptr(), other._flat().data_ptr(),
-            self._local_array.numel(), ws.data_ptr(), out.data_ptr(),
-            self._dt()), "dot")
-        self._sub_comm.allreduce_(out[:1], "sum")
-        return np.float64(out[0].item())
-
-    def _norm_local(self, op: int, p: float) -> torch.Tensor:
-        ws, out = _reduce_buffers(self._local_array.device)
-        _ffi.checked(_ffi.lib().pam_norm_local(
-            self._stream(), self._flat().data_ptr(),
-            self._local_array.numel(), op, p, ws.data_ptr(), out.data_ptr(),
-            self._dt()), "norm")
-        return out[:1]
+        out = kernels.dot(self._local_array, other._local_array)
+        self._sub_comm.allreduce_(out, "sum")
+        return np.float64(out.item())
 
     def norm(self, ord: Optional[float] = None,
              axis: Optional[int] = None):
@@ -669,21 +554,14 @@ class DistributedArray:
         ord = 2 if ord is None else ord
         if ord in ("fro", "nuc"):
             raise ValueError(f"norm-{ord} not possible for vectors")
-        if ord == 0:
-            out = self._norm_local(3, 0.0)
-            self._sub_comm.allreduce_(out, "sum")
-            return np.float64(out.item())
-        if ord == np.inf:
-            out = self._norm_local(1, 0.0)
-            self._sub_comm.allreduce_(out, "max")
-            return np.float64(out.item())
-        if ord == -np.inf:
-            out = self._norm_local(2, 0.0)
-            self._sub_comm.allreduce_(out, "min")
-            return np.float64(out.item())
-        out = self._norm_local(0, float(ord))
-        self._sub_comm.allreduce_(out, "sum")
-        return np.float64(out.item() ** (1.0 / ord))
+        # pam_norm_local op, its p, and the cross-rank reduction
+        op, p, red = {0: (3, 0.0, "sum"), np.inf: (1, 0.0, "max"),
+                      -np.inf: (2, 0.0, "min")}.get(
+                          ord, (0, float(ord), "sum"))
+        out = kernels.norm_local(self._local_array, op, p)
+        self._sub_comm.allreduce_(out, red)
+        return np.float64(out.item() ** (1.0 / ord) if op == 0
+                          else out.item())
 
     def _norm_axis(self, ord, axis: int) -> torch.Tensor:
         """Per-axis norms (ref :719-771 _compute_vector_norm + :828-838).
@@ -741,11 +619,8 @@ class DistributedArray:
         # ref cls_basic.py:389-401); treat the result as read-only.
         if not self._is_cplx():
             return self._like(self._local_array)
-        self._require_compute()
         out = self._like()
-        _ffi.checked(_ffi.lib().pam_conj(
-            self._stream(), out._flat().data_ptr(), self._flat().data_ptr(),
-            self._local_array.numel(), self._dt()), "conj")
+        kernels.conj(out._local_array, self._local_array)
         return out
 
     def copy(self):

@@ -7,7 +7,7 @@ block of shape ``dims``."""
 import numpy as np
 import torch
 
-from . import _ffi
+from . import kernels
 from .derivative import _FD1_OPS, _FD2_OPS
 from .localops import LocalOperator
 
@@ -32,28 +32,10 @@ class _FDLocalBase(LocalOperator):
         self.m = int(np.prod(self.dims[axis + 1:], initial=1))
 
     def _run(self, x: torch.Tensor, op: int) -> torch.Tensor:
-        if x.device.type != "cuda":
-            raise RuntimeError(
-                "pam: compute ops require a CUDA (MI355X) device tensor — "
-                "there is no CPU compute path")
-        flat = x.reshape(-1).contiguous()
-        y = torch.empty_like(flat)
-        batch, d, m = self.batch, self.d, self.m
-        if flat.is_complex():
-            rb, rm = batch, 2 * m  # componentwise on the interleaved view
-            xr = torch.view_as_real(flat).reshape(-1)
-            yr = torch.view_as_real(y).reshape(-1)
-            dt = _ffi.dtype_code(xr.dtype)
-            ptrs = (xr.data_ptr(), yr.data_ptr())
-        else:
-            rb, rm = batch, m
-            dt = _ffi.dtype_code(flat.dtype)
-            ptrs = (flat.data_ptr(), y.data_ptr())
-        stream = torch.cuda.current_stream(x.device).cuda_stream
-        _ffi.checked(_ffi.lib().pam_fd_serial(
-            stream, op, 1 if self.edge else 0, ptrs[0], ptrs[1], rb, d, rm,
-            self._coeff(), dt), "fd_serial")
-        return y
+        x = x.reshape(self.batch, self.d, self.m)
+        y = torch.empty(x.shape, dtype=x.dtype, device=x.device)
+        kernels.fd_serial(y, x, op, self.edge, self._coeff())
+        return y.view(-1)
 
     def matvec(self, x):
         return self._run(x, self._op_mv)

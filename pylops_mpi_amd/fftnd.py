@@ -22,21 +22,13 @@ from typing import Optional, Sequence, Union
 import numpy as np
 import torch
 
+from . import kernels
 from .comm import PamComm
-from .distributedarray import DistributedArray, Partition
+from .distributedarray import (DistributedArray, Partition, as_numpy_dtype,
+                               as_torch_dtype, local_split)
 from .fft_helper import fftshift_nd, ifftshift_nd
 from .linearoperator import MPILinearOperator
 from .rebalance import rebalance_1d
-
-_REAL_OF = {np.dtype(np.complex128): np.float64,
-            np.dtype(np.complex64): np.float32,
-            np.dtype(np.float64): np.float64,
-            np.dtype(np.float32): np.float32}
-_CPLX_OF = {np.dtype(np.float64): np.complex128,
-            np.dtype(np.float32): np.complex64,
-            np.dtype(np.complex128): np.complex128,
-            np.dtype(np.complex64): np.complex64}
-
 
 def _as_int_tuple(v) -> tuple:
     if isinstance(v, Integral):
@@ -128,8 +120,8 @@ class _MPIBaseFFTND(MPILinearOperator):
             dimsd[self.axes[-1]] = self.nffts[-1] // 2 + 1
         self.dimsd = tuple(int(d) for d in dimsd)
         dtype = np.dtype(dtype)
-        self.rdtype = np.dtype(_REAL_OF[dtype]) if self.real else dtype
-        self.cdtype = np.dtype(_CPLX_OF[dtype])
+        self.rdtype = np.empty(0, dtype).real.dtype if self.real else dtype
+        self.cdtype = np.result_type(dtype, np.complex64)
         self.clinear = not (self.real
                             or np.issubdtype(dtype, np.floating))
         super().__init__(dtype=self.cdtype, dims=tuple(self.dims),
@@ -163,13 +155,12 @@ class MPIFFTND(_MPIBaseFFTND):
         if x.partition is not Partition.SCATTER:
             raise ValueError(f"x should have partition={Partition.SCATTER}, "
                              f"{x.partition} != {Partition.SCATTER}")
-        from .distributedarray import local_split
         size = x.base_comm.size
         lshapes = [local_split(tuple(shape), size, r, Partition.SCATTER, 0)
                    for r in range(size)]
         counts = [int(np.prod(s)) for s in lshapes]
         t = rebalance_1d(x, counts).reshape(lshapes[x.rank])
-        if copy and t.data_ptr() == x.local_array.data_ptr():
+        if copy and kernels.same_memory(t, x.local_array):
             t = t.clone()
         return DistributedArray(tuple(shape), x.base_comm,
                                 Partition.SCATTER, 0, local_array=t,
@@ -264,7 +255,7 @@ class MPIFFTND(_MPIBaseFFTND):
             return DistributedArray(
                 tuple(t.shape), like.base_comm, Partition.SCATTER,
                 like.axis, local_array=t, engine="hip",
-                dtype=_t2np(t.dtype))
+                dtype=as_numpy_dtype(t.dtype))
         axis = like.axis
         gshape = list(like.global_shape)
         lshapes = [list(s) for s in like.local_shapes]
@@ -278,7 +269,7 @@ class MPIFFTND(_MPIBaseFFTND):
         return DistributedArray(
             tuple(gshape), like.base_comm, Partition.SCATTER, axis,
             local_array=t, local_shapes=[tuple(s) for s in lshapes],
-            engine="hip", dtype=_t2np(t.dtype))
+            engine="hip", dtype=as_numpy_dtype(t.dtype))
 
     def _scale_real_fft(self, x: DistributedArray,
                         inverse: bool = False) -> None:
@@ -322,8 +313,8 @@ class MPIFFTND(_MPIBaseFFTND):
             self._scale_real_fft(y, inverse=False)
         if self.norm == "1/n":
             y.local_array.mul_(self._scale)
-        if np.dtype(_t2np(y.local_array.dtype)) != self.cdtype:
-            y = self._wrap(y, y.local_array.to(_np2t(self.cdtype)))
+        if as_numpy_dtype(y.local_array.dtype) != self.cdtype:
+            y = self._wrap(y, y.local_array.to(as_torch_dtype(self.cdtype)))
         if self.fftshift_after.any():
             y = fftshift_nd(
                 y, axes=[int(a) for a in self.axes[self.fftshift_after]])
@@ -344,8 +335,8 @@ class MPIFFTND(_MPIBaseFFTND):
             y.local_array.mul_(self._scale)
         if not self.clinear and y.local_array.is_complex():
             y = self._wrap(y, y.local_array.real.contiguous())
-        if np.dtype(_t2np(y.local_array.dtype)) != self.rdtype:
-            y = self._wrap(y, y.local_array.to(_np2t(self.rdtype)))
+        if as_numpy_dtype(y.local_array.dtype) != self.rdtype:
+            y = self._wrap(y, y.local_array.to(as_torch_dtype(self.rdtype)))
         if self.ifftshift_before.any():
             y = fftshift_nd(
                 y, axes=[int(a) for a in self.axes[self.ifftshift_before]])
@@ -376,19 +367,3 @@ class MPIFFT2D(MPIFFTND):
                          base_comm=base_comm)
         self.f1, self.f2 = self.fs
         del self.fs
-
-
-_T2NP = {torch.float64: np.float64, torch.float32: np.float32,
-         torch.complex128: np.complex128, torch.complex64: np.complex64}
-_NP2T = {np.dtype(np.float64): torch.float64,
-         np.dtype(np.float32): torch.float32,
-         np.dtype(np.complex128): torch.complex128,
-         np.dtype(np.complex64): torch.complex64}
-
-
-def _t2np(td):
-    return _T2NP[td]
-
-
-def _np2t(npd):
-    return _NP2T[np.dtype(npd)]

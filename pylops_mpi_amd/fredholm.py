@@ -12,14 +12,10 @@ from typing import Optional
 import numpy as np
 import torch
 
-from . import _ffi
+from . import kernels
 from .comm import PamComm, get_default_comm
 from .distributedarray import DistributedArray, Partition, as_torch_dtype
 from .linearoperator import MPILinearOperator
-
-
-def _stream(t):
-    return torch.cuda.current_stream(t.device).cuda_stream
 
 
 class MPIFredholm1(MPILinearOperator):
@@ -52,32 +48,14 @@ class MPIFredholm1(MPILinearOperator):
     def _batched(self, A: torch.Tensor, X: torch.Tensor, opa: int
                  ) -> torch.Tensor:
         """Y_b = op(A_b) @ X_b for every local slice."""
-        if A.device.type != "cuda":
-            raise RuntimeError(
-                "pam: compute ops require a CUDA (MI355X) device tensor — "
-                "there is no CPU compute path")
-        batch = A.shape[0]
-        if opa:
-            K, M = int(A.shape[1]), int(A.shape[2])
-        else:
-            M, K = int(A.shape[1]), int(A.shape[2])
-        N = int(X.shape[2])
-        Y = torch.empty((batch, M, N), dtype=A.dtype, device=A.device)
-        A, X = A.contiguous(), X.contiguous()
-        if A.is_complex():
-            _ffi.checked(_ffi.lib().pam_cgemm_batched(
-                _stream(A), A.data_ptr(), X.data_ptr(), Y.data_ptr(), batch,
-                M, N, K, A.shape[1] * A.shape[2], K * N, M * N, opa, 0,
-                _ffi.dtype_code(A.dtype)), "cgemm_batched")
-        else:
-            # real dtypes: one z-batched MFMA launch (opa=1 loads A
-            # transposed in-kernel; conj is a no-op on reals).  The r01
-            # form looped pam_gemm per slice from Python — 4-workgroup
-            # launches, chip empty.
-            _ffi.checked(_ffi.lib().pam_gemm_batched(
-                _stream(A), A.data_ptr(), X.data_ptr(), Y.data_ptr(),
-                batch, M, N, K, A.shape[1] * A.shape[2], K * N, M * N,
-                opa, 0, _ffi.dtype_code(A.dtype)), "gemm_batched")
+        M = int(A.shape[2] if opa else A.shape[1])
+        Y = torch.empty((A.shape[0], M, int(X.shape[2])), dtype=A.dtype,
+                        device=A.device)
+        # complex: batched MFMA cgemm; real dtypes: one z-batched MFMA
+        # launch (opa=1 loads A transposed in-kernel; conj is a no-op on
+        # reals).  The r01 form looped pam_gemm per slice from Python —
+        # 4-workgroup launches, chip empty.
+        kernels.gemm_batched(Y, A, X, opa=bool(opa))
         return Y
 
     # ------------------------------------------------------------- applies

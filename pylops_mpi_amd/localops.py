@@ -11,20 +11,7 @@ from typing import Callable, Optional, Tuple
 import numpy as np
 import torch
 
-from . import _ffi
-
-# per-device GEMV scratch, sized for the largest (nr, nc) seen
-_gemv_ws = {}
-
-
-def _gemv_buffer(device, nr: int, nc: int) -> torch.Tensor:
-    need = int(_ffi.lib().pam_gemv_ws_elems(nr, nc))
-    key = (device.type, device.index)
-    ws = _gemv_ws.get(key)
-    if ws is None or ws.numel() < need:
-        ws = torch.empty(need, dtype=torch.float64, device=device)
-        _gemv_ws[key] = ws
-    return ws
+from . import kernels
 
 
 class LocalOperator:
@@ -62,43 +49,24 @@ class DenseLocal(LocalOperator):
         self.dtype = np.dtype(
             {torch.float64: np.float64, torch.float32: np.float32}[A.dtype])
 
-    def _gemv(self, A: torch.Tensor, x: torch.Tensor, trans: int,
+    def _gemv(self, A: torch.Tensor, x: torch.Tensor, trans: bool,
               nout: int) -> torch.Tensor:
-        if A.device.type != "cuda":
-            raise RuntimeError(
-                "pam: compute ops require a CUDA (MI355X) device tensor — "
-                "there is no CPU compute path")
-        nr, nc = int(A.shape[0]), int(A.shape[1])
         out = torch.empty(nout, dtype=A.dtype, device=A.device)
-        ws = _gemv_buffer(A.device, nr, nc)
-        stream = torch.cuda.current_stream(A.device).cuda_stream
-        _ffi.checked(_ffi.lib().pam_gemv(
-            stream, trans, A.data_ptr(), x.contiguous().data_ptr(),
-            out.data_ptr(), nr, nc, ws.data_ptr(),
-            _ffi.dtype_code(A.dtype)), "gemv")
+        kernels.gemv(out, A, x, trans)
         return out
 
     def matvec(self, x: torch.Tensor) -> torch.Tensor:
-        return self._gemv(self.A, x.reshape(-1), 0, self.shape[0])
+        return self._gemv(self.A, x, False, self.shape[0])
 
     def rmatvec(self, x: torch.Tensor) -> torch.Tensor:
         if self.saveAt:
             if self._At is None:
-                if self.A.device.type != "cuda":
-                    raise RuntimeError(
-                        "pam: compute ops require a CUDA (MI355X) device "
-                        "tensor — there is no CPU compute path")
                 At = torch.empty((self.shape[1], self.shape[0]),
                                  dtype=self.A.dtype, device=self.A.device)
-                stream = torch.cuda.current_stream(
-                    self.A.device).cuda_stream
-                _ffi.checked(_ffi.lib().pam_transpose(
-                    stream, self.A.data_ptr(), At.data_ptr(),
-                    self.shape[0], self.shape[1],
-                    _ffi.dtype_code(self.A.dtype)), "transpose")
+                kernels.transpose(At, self.A)
                 self._At = At
-            return self._gemv(self._At, x.reshape(-1), 0, self.shape[1])
-        return self._gemv(self.A, x.reshape(-1), 1, self.shape[1])
+            return self._gemv(self._At, x, False, self.shape[1])
+        return self._gemv(self.A, x, True, self.shape[1])
 
 
 class AdjointLocal(LocalOperator):

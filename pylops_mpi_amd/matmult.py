@@ -44,13 +44,10 @@ from typing import Optional, Tuple
 import numpy as np
 import torch
 
-from . import _ffi
+from . import kernels
 from .comm import PamComm, get_default_comm
 from .distributedarray import DistributedArray, Partition, as_torch_dtype
 from .linearoperator import MPILinearOperator
-
-def _stream(t: torch.Tensor):
-    return torch.cuda.current_stream(t.device).cuda_stream
 
 
 def active_grid_comm(base_comm: PamComm, N: int, M: int):
@@ -157,49 +154,20 @@ class _MatMultBase(MPILinearOperator):
     def _local_gemm(self, A: torch.Tensor, B: torch.Tensor,
                     C: Optional[torch.Tensor] = None,
                     accumulate: bool = False) -> torch.Tensor:
-        M, K = A.shape
-        K2, N = B.shape
-        assert K == K2
         if C is None:
-            C = torch.empty((M, N), dtype=A.dtype, device=A.device)
-        if A.device.type != "cuda":
-            raise RuntimeError(
-                "pam: compute ops require a CUDA (MI355X) device tensor — "
-                "there is no CPU compute path")
-        if A.is_complex():
-            # complex panels: the batched MFMA cgemm with batch=1
-            # (ref MatrixMult.py supports complex dtypes throughout)
-            _ffi.checked(_ffi.lib().pam_cgemm_batched(
-                _stream(A), A.contiguous().data_ptr(),
-                B.contiguous().data_ptr(), C.data_ptr(), 1, M, N, K,
-                0, 0, 0, 0, 1 if accumulate else 0,
-                _ffi.dtype_code(A.dtype)), "cgemm")
-        else:
-            _ffi.checked(_ffi.lib().pam_gemm(
-                _stream(A), A.contiguous().data_ptr(),
-                B.contiguous().data_ptr(), C.data_ptr(), M, N, K, K, N, N,
-                1 if accumulate else 0, _ffi.dtype_code(A.dtype)), "gemm")
+            C = torch.empty((A.shape[0], B.shape[1]), dtype=A.dtype,
+                            device=A.device)
+        # complex panels: the batched MFMA cgemm with batch=1
+        # (ref MatrixMult.py supports complex dtypes throughout)
+        kernels.gemm(C, A, B, accumulate)
         return C
 
     def _local_transpose(self, A: torch.Tensor) -> torch.Tensor:
         """A^T for real dtypes, A^H for complex (ref :317-318,416,737
         ``A.T.conj()`` — conj is a no-op on reals)."""
-        if A.device.type != "cuda":
-            raise RuntimeError(
-                "pam: compute ops require a CUDA (MI355X) device tensor — "
-                "there is no CPU compute path")
         At = torch.empty((A.shape[1], A.shape[0]), dtype=A.dtype,
                          device=A.device)
-        if A.is_complex():
-            _ffi.checked(_ffi.lib().pam_ctranspose(
-                _stream(A), A.contiguous().data_ptr(), At.data_ptr(),
-                A.shape[0], A.shape[1], 1, _ffi.dtype_code(A.dtype)),
-                "ctranspose")
-        else:
-            _ffi.checked(_ffi.lib().pam_transpose(
-                _stream(A), A.contiguous().data_ptr(), At.data_ptr(),
-                A.shape[0], A.shape[1], _ffi.dtype_code(A.dtype)),
-                "transpose")
+        kernels.transpose(At, A, conj=True)
         return At
 
     def _AH(self) -> torch.Tensor:

@@ -26,8 +26,10 @@ import logging
 import numpy as np
 import torch
 
+from . import kernels
 from .comm import PamComm, get_default_comm
-from .distributedarray import DistributedArray, Partition
+from .distributedarray import (DistributedArray, Partition, as_numpy_dtype,
+                               as_torch_dtype)
 from .fredholm import MPIFredholm1
 from .linearoperator import MPILinearOperator
 
@@ -41,8 +43,9 @@ def MPIMDC(G: torch.Tensor, nt: int, nv: int, nfreq: int, dt: float = 1.0,
     if twosided and nt % 2 == 0:
         raise ValueError('nt must be odd number')
 
-    dtype = np.dtype({torch.complex64: np.complex64,
-                      torch.complex128: np.complex128}[G.dtype])
+    if not G.is_complex():
+        raise KeyError(f"MPIMDC needs a complex kernel G, got {G.dtype}")
+    dtype = as_numpy_dtype(G.dtype)
     rdtype = np.real(np.ones(1, dtype=dtype)).dtype
 
     # Fredholm kernel, prescaled (ref :36-43).  The EXTRA 1/nt folds the
@@ -90,6 +93,8 @@ class _FusedMDC(MPILinearOperator):
         self.twosided = bool(twosided)
         self.rdtype = np.dtype(rdtype)
         self.cdtype = np.dtype(cdtype)
+        self._rt = as_torch_dtype(self.rdtype)
+        self._ct = as_torch_dtype(self.cdtype)
         # conjugate-twin bins: 0 < k < nt - k (fftlocal.py:47-48)
         self._tw0, self._tw1 = 1, (nt + 1) // 2
         super().__init__(shape=(nt * ns * nv, nt * nr * nv), dtype=rdtype,
@@ -100,16 +105,7 @@ class _FusedMDC(MPILinearOperator):
         flat = t.reshape(-1)
         return DistributedArray(
             (int(flat.numel()),), self.base_comm, Partition.BROADCAST,
-            local_array=flat,
-            dtype=np.dtype({torch.complex64: np.complex64,
-                            torch.complex128: np.complex128,
-                            torch.float32: np.float32,
-                            torch.float64: np.float64}[t.dtype]))
-
-    @property
-    def _rt(self):
-        return torch.float32 if self._CT[self.cdtype] == torch.complex64 \
-            else torch.float64
+            local_array=flat, dtype=as_numpy_dtype(t.dtype))
 
     # PAM_MDC_FFT=strided falls back to the strided rocFFT plans (the
     # r02 A/B loser at the cfg5 shape: rocFFT's strided real plans run
@@ -129,49 +125,34 @@ class _FusedMDC(MPILinearOperator):
         1/sqrt(nt) of both directions folds into G (MPIMDC factory) —
         exact operator algebra, parity-tested.  Standalone FFT
         operators (fftlocal.FFTLocal) keep the full convention."""
-        from . import _ffi
         t = x.local_array.reshape(self.nt, nmid * self.nv)
         m = t.shape[1]
-        stream = torch.cuda.current_stream(t.device).cuda_stream
-        ct = self._CT[self.cdtype]
-        rcode = _ffi.dtype_code(self._rt)
+        ct, rt, dev = self._ct, self._rt, t.device
         if self._CONTIG:
             # complex (nt, m) -> real (m, nt), transpose fused with the
             # real extraction
-            r = torch.empty((m, self.nt), device=t.device, dtype=self._rt)
+            r = torch.empty((m, self.nt), device=dev, dtype=rt)
             if t.is_complex():
-                _ffi.checked(_ffi.lib().pam_unzip_t(
-                    stream, r.data_ptr(), t.contiguous().data_ptr(),
-                    self.nt, m, _ffi.dtype_code(t.dtype)), "unzip_t")
+                kernels.unzip(r, t, transposed=True)
             else:
-                _ffi.checked(_ffi.lib().pam_transpose(
-                    stream, t.to(self._rt).contiguous().data_ptr(),
-                    r.data_ptr(), self.nt, m, rcode), "transpose")
+                kernels.transpose(r, t.to(rt))
             if shift:
                 r = torch.fft.ifftshift(r, dim=1)
-            F = torch.empty((m, self.nfft), device=t.device, dtype=ct)
-            _ffi.checked(_ffi.lib().pam_rfft_contig(
-                stream, r.contiguous().data_ptr(), F.data_ptr(), self.nt,
-                m, rcode), "rfft_contig")
-            f = torch.empty((self.nfft, m), device=t.device, dtype=ct)
-            _ffi.checked(_ffi.lib().pam_ctranspose(
-                stream, F.data_ptr(), f.data_ptr(), m, self.nfft, 0,
-                _ffi.dtype_code(ct)), "ctranspose")
+            F = torch.empty((m, self.nfft), device=dev, dtype=ct)
+            kernels.rfft(F, r, contig=True)
+            f = torch.empty((self.nfft, m), device=dev, dtype=ct)
+            kernels.transpose(f, F)
             return f
         if t.is_complex():
-            r = torch.empty(t.shape, device=t.device, dtype=self._rt)
-            _ffi.checked(_ffi.lib().pam_unzip(
-                stream, r.data_ptr(), t.contiguous().data_ptr(),
-                t.numel(), _ffi.dtype_code(t.dtype)), "unzip")
+            r = torch.empty(t.shape, device=dev, dtype=rt)
+            kernels.unzip(r, t)
             t = r
         else:
-            t = t.to(self._rt)
+            t = t.to(rt)
         if shift:
             t = torch.fft.ifftshift(t, dim=0)
-        f = torch.empty((self.nfft, m), device=t.device, dtype=ct)
-        _ffi.checked(_ffi.lib().pam_rfft_strided(
-            stream, t.contiguous().data_ptr(), f.data_ptr(), self.nt, m,
-            rcode), "rfft_strided")
+        f = torch.empty((self.nfft, m), device=dev, dtype=ct)
+        kernels.rfft(f, t, contig=False)
         return f
 
     def _inv_fft(self, fr: torch.Tensor, nmid: int,
@@ -179,48 +160,30 @@ class _FusedMDC(MPILinearOperator):
         """zero-pad + irfft + complex carrier -> (nt, m) complex (the
         composite chain's stage wrappers carry complex storage end to
         end — mirrored)."""
-        from . import _ffi
         m = nmid * self.nv
-        ct = self._CT[self.cdtype]
-        rcode = _ffi.dtype_code(self._rt)
-        stream = torch.cuda.current_stream(fr.device).cuda_stream
+        ct, rt, dev = self._ct, self._rt, fr.device
         # zero-pad the masked bins back to nfft (IdentityLocal adjoint)
         if self.nfreq == self.nfft:
             z = fr.reshape(self.nfft, m)  # fr is fresh (clobberable)
         else:
-            z = torch.zeros(self.nfft, m, dtype=fr.dtype,
-                            device=fr.device)
+            z = torch.zeros(self.nfft, m, dtype=fr.dtype, device=dev)
             z[: self.nfreq] = fr.reshape(self.nfreq, m)
+        out = torch.empty((self.nt, m), device=dev, dtype=ct)
         if self._CONTIG:
-            Zt = torch.empty((m, self.nfft), device=z.device, dtype=ct)
-            _ffi.checked(_ffi.lib().pam_ctranspose(
-                stream, z.contiguous().data_ptr(), Zt.data_ptr(),
-                self.nfft, m, 0, _ffi.dtype_code(ct)), "ctranspose")
-            r = torch.empty((m, self.nt), device=z.device, dtype=self._rt)
-            _ffi.checked(_ffi.lib().pam_irfft_contig(
-                stream, Zt.data_ptr(), r.data_ptr(), self.nt, m, rcode),
-                "irfft_contig")
+            Zt = torch.empty((m, self.nfft), device=dev, dtype=ct)
+            kernels.transpose(Zt, z)
+            r = torch.empty((m, self.nt), device=dev, dtype=rt)
+            kernels.irfft(r, Zt, contig=True)
             if shift:
                 r = torch.fft.fftshift(r, dim=1)
-            out = torch.empty((self.nt, m), device=z.device, dtype=ct)
-            _ffi.checked(_ffi.lib().pam_zip_t(
-                stream, out.data_ptr(), r.contiguous().data_ptr(),
-                self.nt, m, _ffi.dtype_code(ct)), "zip_t")
+            kernels.zip(out, r, transposed=True)
             return out
-        r = torch.empty((self.nt, m), device=z.device, dtype=self._rt)
-        _ffi.checked(_ffi.lib().pam_irfft_strided(
-            stream, z.contiguous().data_ptr(), r.data_ptr(), self.nt, m,
-            rcode), "irfft_strided")
+        r = torch.empty((self.nt, m), device=dev, dtype=rt)
+        kernels.irfft(r, z, contig=False)
         if shift:
             r = torch.fft.fftshift(r, dim=0)
-        out = torch.empty((self.nt, m), device=z.device, dtype=ct)
-        _ffi.checked(_ffi.lib().pam_zip(
-            stream, out.data_ptr(), r.contiguous().data_ptr(),
-            r.numel(), _ffi.dtype_code(ct)), "zip")
+        kernels.zip(out, r)
         return out
-
-    _CT = {np.dtype(np.complex64): torch.complex64,
-           np.dtype(np.complex128): torch.complex128}
 
     def _matvec(self, x: DistributedArray) -> DistributedArray:
         f = self._fwd_fft(x, self.nr, self.twosided)       # Fop

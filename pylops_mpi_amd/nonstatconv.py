@@ -13,7 +13,7 @@ from typing import Optional, Tuple, Union
 import numpy as np
 import torch
 
-from . import _ffi
+from . import kernels
 from .blockdiag import MPIBlockDiag
 from .comm import PamComm, get_default_comm
 from .halo import MPIHalo
@@ -72,19 +72,10 @@ class NonStationaryConvolve1DLocal(LocalOperator):
         self.m = int(np.prod(self.dims[axis + 1:], initial=1))
 
     def _run(self, x: torch.Tensor, forward: bool) -> torch.Tensor:
-        if x.device.type != "cuda":
-            raise RuntimeError(
-                "pam: compute ops require a CUDA (MI355X) device tensor — "
-                "there is no CPU compute path")
-        flat = x.reshape(-1).contiguous()
-        y = torch.empty_like(flat)
-        stream = torch.cuda.current_stream(x.device).cuda_stream
-        _ffi.checked(_ffi.lib().pam_nsconv(
-            stream, 1 if forward else 0, flat.data_ptr(), y.data_ptr(),
-            self.hs.data_ptr(), self.batch, self.d, self.m,
-            self.hs.shape[0], self.hs.shape[1], self.oh, self.dh,
-            _ffi.dtype_code(flat.dtype)), "nsconv")
-        return y
+        x = x.reshape(self.batch, self.d, self.m)
+        y = torch.empty(x.shape, dtype=x.dtype, device=x.device)
+        kernels.nsconv(y, x, self.hs, forward, self.oh, self.dh)
+        return y.view(-1)
 
     def matvec(self, x):
         return self._run(x, True)

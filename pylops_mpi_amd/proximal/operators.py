@@ -29,7 +29,7 @@ from typing import Any, Callable, Optional
 import numpy as np
 import torch
 
-from .. import _ffi
+from .. import kernels
 from ..distributedarray import DistributedArray, Partition
 from ..linearoperator import MPILinearOperator
 from ..blockdiag import MPIBlockDiag
@@ -40,15 +40,8 @@ from ..vstack import MPIStackedVStack
 
 
 def _thresh_tensor(x: torch.Tensor, kind: int, thresh: float) -> torch.Tensor:
-    if not x.is_cuda:
-        raise RuntimeError(
-            "pylops_mpi_amd.proximal thresholds run the HIP pam_thresh "
-            "kernel and need a CUDA tensor (no CPU fallback)")
-    out = torch.empty_like(x)
-    stream = torch.cuda.current_stream(x.device).cuda_stream
-    _ffi.checked(_ffi.lib().pam_thresh(
-        stream, out.data_ptr(), x.data_ptr(), x.numel(), kind,
-        float(thresh), _ffi.dtype_code(x.dtype)), "thresh")
+    out = torch.empty(x.shape, dtype=x.dtype, device=x.device)
+    kernels.thresh(out, x, kind, thresh)
     return out
 
 

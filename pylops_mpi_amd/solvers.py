@@ -35,7 +35,7 @@ from typing import Optional, Tuple
 
 import numpy as np
 
-from . import _ffi, deps
+from . import deps, kernels
 from .distributedarray import DistributedArray, Partition
 
 
@@ -100,20 +100,16 @@ class CG:
     def _step_dev(self, x: DistributedArray):
         """ref :110-141 with device-resident scalars (module docstring);
         one host sync per iteration (the k readback for the stop test)."""
-        B, lib, s = self._B, _ffi.lib(), self.c._stream()
+        B = self._B
         Opc = self.Op.matvec(self.c)
         self.c.dot_into(Opc, B[0:1])
         x._sub_comm.allreduce_(B[0:1], "sum")
-        _ffi.checked(lib.pam_scalar_alpha(          # a = |kold / cOpc|
-            s, B[2:3].data_ptr(), B[7:8].data_ptr(), B[0:2].data_ptr(), 0.0),
-            "scalar_alpha")
+        kernels.scalar_alpha(B[2:3], B[7:8], B[0:2], 0.0)  # a = |kold / cOpc|
         x.iaxpy_dev_(B[2:3], self.c)                # x += a * c
         self.r.iaxpy_dev_(B[2:3], Opc, -1.0)        # r -= a * Opc
         self.r.dot_into(self.r, B[4:5])
         x._sub_comm.allreduce_(B[4:5], "sum")
-        _ffi.checked(lib.pam_scalar_div(            # b = k / kold
-            s, B[3:4].data_ptr(), B[4:5].data_ptr(), B[7:8].data_ptr()),
-            "scalar_div")
+        kernels.scalar_div(B[3:4], B[4:5], B[7:8])  # b = k / kold
         B[7:8].copy_(B[4:5])                        # kold <- k (device)
         self.c.xpby_dev_(self.r, B[3:4])            # c = r + b * c
         self.kold = abs(float(B[4].item()))         # the ONE sync: stop test
@@ -206,13 +202,12 @@ class CGLS:
         """ref :370-404 with device-resident scalars (module docstring);
         one host sync per iteration (the k/ss/xx readback: stop test +
         cost/cost1 bookkeeping, ref :398-403)."""
-        B, lib, s = self._B, _ffi.lib(), self.c._stream()
+        B = self._B
         self.q.dot_into(self.q, B[0:1])             # q.q
         self.c.dot_into(self.c, B[1:2])             # c.c
         x._sub_comm.allreduce_(B[0:2], "sum")       # one collective for both
-        _ffi.checked(lib.pam_scalar_alpha(          # a = |kold/(qq+damp^2 cc)|
-            s, B[2:3].data_ptr(), B[7:8].data_ptr(), B[0:2].data_ptr(),
-            self.damp), "scalar_alpha")
+        # a = |kold / (qq + damp^2 cc)|
+        kernels.scalar_alpha(B[2:3], B[7:8], B[0:2], self.damp)
         x.iaxpy_dev_(B[2:3], self.c)                # x += a * c   (ref :390)
         self.s.iaxpy_dev_(B[2:3], self.q, -1.0)     # s -= a * q   (ref :391)
         r = self.Op.rmatvec(self.s)
@@ -222,9 +217,7 @@ class CGLS:
         self.s.dot_into(self.s, B[5:6])             # |s|^2   (cost)
         x.dot_into(x, B[6:7])                       # |x|^2   (cost1)
         x._sub_comm.allreduce_(B[4:7], "sum")       # one collective for all 3
-        _ffi.checked(lib.pam_scalar_div(            # b = k / kold
-            s, B[3:4].data_ptr(), B[4:5].data_ptr(), B[7:8].data_ptr()),
-            "scalar_div")
+        kernels.scalar_div(B[3:4], B[4:5], B[7:8])  # b = k / kold
         B[7:8].copy_(B[4:5])                        # kold <- k (device)
         self.c.xpby_dev_(r, B[3:4])                 # c = r + b * c (ref :396)
         self.q = self.Op.matvec(self.c)

@@ -10,7 +10,7 @@ from typing import Optional, Tuple, Union
 
 import numpy as np
 
-from . import _ffi
+from . import kernels
 from .distributedarray import DistributedArray
 from .solvers import power_iteration
 from .stacked import StackedDistributedArray
@@ -19,11 +19,7 @@ _THRESH_KINDS = {"soft": 0, "hard": 1, "half": 2}
 
 
 def _thresh_inplace(d: DistributedArray, kind: int, thresh: float):
-    d._require_compute()
-    flat = d._flat()
-    _ffi.checked(_ffi.lib().pam_thresh(
-        d._stream(), flat.data_ptr(), flat.data_ptr(),
-        d.local_array.numel(), kind, float(thresh), d._dt()), "thresh")
+    kernels.thresh(d.local_array, d.local_array, kind, thresh)
     return d
 
 

@@ -53,3 +53,41 @@ def test_ffi_binding_covers_header():
     from pylops_mpi_amd import _ffi
     for sym in header_symbols():
         assert sym in _ffi._SIGS, f"{sym} not bound in _ffi"
+
+
+_CTYPE_OF = {"void*": ctypes.c_void_p, "const void*": ctypes.c_void_p,
+             "int64_t": ctypes.c_int64, "int": ctypes.c_int,
+             "double": ctypes.c_double}
+
+
+def header_declarations():
+    """{name: ([argument ctypes], return ctype)} parsed from pam.h."""
+    src = re.sub(r"/\*.*?\*/", " ", open(HEADER).read(), flags=re.S)
+    decls = {}
+    for ret, name, args in re.findall(
+            r"\b(int64_t|int)\s+(pam_\w+)\s*\(([^)]*)\)\s*;", src):
+        argtypes = []
+        for arg in args.split(","):
+            arg = " ".join(arg.split())
+            if arg == "void":
+                continue
+            # "const void* x" -> type "const void*", name "x"
+            ctype, argname = arg.replace("*", "* ").rsplit(None, 1)
+            assert re.fullmatch(r"\w+", argname), arg
+            argtypes.append(_CTYPE_OF[ctype.replace(" *", "*")])
+        decls[name] = (argtypes, _CTYPE_OF[ret])
+    return decls
+
+
+def test_ffi_signatures_match_header():
+    """Every _ffi._SIGS entry restates its pam.h declaration exactly —
+    a c_int against an int64_t would corrupt arguments silently."""
+    import sys
+    sys.path.insert(0, ROOT)
+    from pylops_mpi_amd import _ffi
+    decls = header_declarations()
+    assert sorted(decls) == header_symbols()
+    for name, sig in decls.items():
+        assert _ffi._SIGS[name] == sig, f"{name}: _SIGS disagrees with pam.h"
+    assert sorted(_ffi._SIGS) == sorted(decls), \
+        "_ffi._SIGS binds names pam.h does not declare"
