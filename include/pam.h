@@ -137,6 +137,46 @@ int pam_norm_local(void* stream, const void* x, int64_t n, int op, double p,
                    void* ws, void* out, int dtype);
 
 /* ------------------------------------------------------------------ *
+ * L2,1 group operators — isotropic total variation.  The group at index
+ * i is (x_0[i], ..., x_{ncomp-1}[i]): the components of a stacked array
+ * (e.g. the output of MPIGradient) travel as PAM_GROUP_MAX pointer slots,
+ * the unused ones NULL.  pyproximal's L21 prox / Euclidean-ball
+ * projection, applied across components without stacking them.
+ *
+ * pam_group_shrink, one pass:
+ *   v_c[i] = a_c[i]                     (all b NULL)
+ *   v_c[i] = a_c[i] + beta * b_c[i]     (two roundings: bitwise equal to
+ *                                        pam_scale followed by pam_add)
+ *   rho    = sqrt(sum_c |v_c[i]|^2)     (c ascending, in the array's real
+ *                                        type; complex: re^2 + im^2)
+ *   mode 0: s = rho > thresh ? (rho - thresh) / rho : 0
+ *           — the prox of thresh * ||.||_{2,1}
+ *   mode 1: s = rho > thresh ? thresh / rho : 1
+ *           — projection on the per-point L2 ball, its Moreau dual
+ *   y_c[i] = v_c[i] * s                 (a zero group gives zeros)
+ * y_c may alias a_c.  n counts elements (complex pairs for complex
+ * dtypes).  PAM_EARG: ncomp outside [1, PAM_GROUP_MAX], a NULL among the
+ * first ncomp y / a, b partly NULL, n < 0, thresh < 0; PAM_EOP: mode not
+ * 0 or 1; all checked before anything is launched.
+ *
+ * pam_group_norm: out[0] = sum_i sqrt(sum_c |x_c[i]|^2), accumulated in
+ * float64 on pam_dot's deterministic tree (`ws`: pam_reduce_ws_elems()
+ * float64 elements); 0 for n == 0.
+ * ------------------------------------------------------------------ */
+#define PAM_GROUP_MAX 4
+int pam_group_shrink(void* stream, int mode, int64_t ncomp,
+                     void* y0, void* y1, void* y2, void* y3,
+                     const void* a0, const void* a1, const void* a2,
+                     const void* a3,
+                     const void* b0, const void* b1, const void* b2,
+                     const void* b3,
+                     double beta, int64_t n, double thresh, int dtype);
+int pam_group_norm(void* stream, int64_t ncomp,
+                   const void* x0, const void* x1, const void* x2,
+                   const void* x3,
+                   int64_t n, void* ws, void* out, int dtype);
+
+/* ------------------------------------------------------------------ *
  * Fused finite-difference stencils along axis 0 of a SCATTER-partitioned
  * array.  One kernel per (operator, kind, direction): no materialized
  * ghost concatenation (the reference copies the whole array per apply,

@@ -55,6 +55,9 @@ _SIGS = {
     "pam_zip": ([P, P, P, L, I], I),
     "pam_gemm_batched": ([P, P, P, P, L, L, L, L, L, L, L, I, I, I], I),
     "pam_norm_local": ([P, P, L, I, D, P, P, I], I),
+    "pam_group_shrink": ([P, I, L, P, P, P, P, P, P, P, P, P, P, P, P, D, L,
+                          D, I], I),
+    "pam_group_norm": ([P, L, P, P, P, P, L, P, P, I], I),
     "pam_gemv_ws_elems": ([L, L], L),
     "pam_gemv": ([P, I, P, P, P, L, L, P, I], I),
     "pam_gemm": ([P, P, P, P, L, L, L, L, L, L, I, I], I),

@@ -876,6 +876,276 @@ extern "C" int pam_norm_local(void* stream, const void* x, int64_t n, int op,
 }
 
 // ---------------------------------------------------------------------------
+// L2,1 group kernels (isotropic TV): the prox couples the NC component
+// arrays of a stacked array at each grid point, so every lane reads the
+// same index of up to PAM_GROUP_MAX arrays — one pass, 16 B per
+// component-point (24 B with the fused shift), nothing materialized.
+//   v_c = a_c (+ beta * b_c),  rho = sqrt(sum_c |v_c|^2),  y_c = v_c * s
+//   mode 0 (prox of thresh*||.||_{2,1}): s = rho > thresh ? (rho-thresh)/rho : 0
+//   mode 1 (projection on the L2 ball) : s = rho > thresh ? thresh/rho     : 1
+// A zero group has rho == 0 <= thresh: s is 0 or 1, never 0/0.
+// NC is a template parameter: the component loops unroll, the pointer
+// arrays stay in SGPRs and all loads issue before the math.  Complex groups
+// span the (re, im) of one element, so complex arrays are NOT launched as
+// their real view (cf. thresh_kernel's CPLX branch); a 16-B vector holds
+// one complex128 or two complex64.  y_c may alias a_c (no __restrict__: an
+// item loads everything it needs before it stores).
+// ---------------------------------------------------------------------------
+template <typename T, int NC>
+struct GroupArgs {
+  T* y[NC];
+  const T* a[NC];
+  const T* b[NC];
+};
+
+template <typename T, int V, bool VEC>
+__device__ __forceinline__ void group_load(const T* p, T* v) {
+  if constexpr (VEC) {
+    loadv<T, V>(p, v);
+  } else {
+#pragma unroll
+    for (int k = 0; k < V; ++k) v[k] = p[k];
+  }
+}
+
+template <typename T, int V, bool VEC>
+__device__ __forceinline__ void group_store(T* p, const T* v) {
+  if constexpr (VEC) {
+    storev<T, V>(p, v);
+  } else {
+#pragma unroll
+    for (int k = 0; k < V; ++k) p[k] = v[k];
+  }
+}
+
+// one work item: V reals (V / E groups) of every component at real offset off
+template <typename T, int NC, int E, int V, bool SHIFT, bool VEC>
+__device__ __forceinline__ void group_shrink_item(const GroupArgs<T, NC>& P,
+                                                  int64_t off, T beta,
+                                                  T thresh, int mode) {
+  T v[NC][V];
+#pragma unroll
+  for (int c = 0; c < NC; ++c) group_load<T, V, VEC>(P.a[c] + off, v[c]);
+  if constexpr (SHIFT) {
+    T w[NC][V];
+#pragma unroll
+    for (int c = 0; c < NC; ++c) group_load<T, V, VEC>(P.b[c] + off, w[c]);
+#pragma unroll
+    for (int c = 0; c < NC; ++c)
+#pragma unroll
+      for (int k = 0; k < V; ++k) {
+        const T t = beta * w[c][k];  // pam_scale's rounding ...
+        v[c][k] = v[c][k] + t;       // ... then pam_add's
+      }
+  }
+#pragma unroll
+  for (int g = 0; g < V / E; ++g) {
+    T acc = (T)0;
+#pragma unroll
+    for (int c = 0; c < NC; ++c) {
+      if constexpr (E == 2)
+        acc += v[c][2 * g] * v[c][2 * g] + v[c][2 * g + 1] * v[c][2 * g + 1];
+      else
+        acc += v[c][g] * v[c][g];
+    }
+    const T rho = sqrt(acc);
+    T s;
+    if (rho > thresh)
+      s = mode ? thresh / rho : (rho - thresh) / rho;
+    else
+      s = mode ? (T)1 : (T)0;
+#pragma unroll
+    for (int c = 0; c < NC; ++c)
+#pragma unroll
+      for (int e = 0; e < E; ++e) v[c][g * E + e] = v[c][g * E + e] * s;
+  }
+#pragma unroll
+  for (int c = 0; c < NC; ++c) group_store<T, V, VEC>(P.y[c] + off, v[c]);
+}
+
+template <typename T, int NC, bool CPLX, bool SHIFT, bool VEC>
+__global__ void __launch_bounds__(BLK) group_shrink_kernel(
+    GroupArgs<T, NC> P, T beta, T thresh, int mode, int64_t n) {
+  constexpr int E = CPLX ? 2 : 1;                  // reals per element
+  constexpr int V = VEC ? VecW<T>::value : E;      // reals per work item
+  const int64_t nv = (n * E) / V;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  for (int64_t i = gid; i < nv; i += stride)
+    group_shrink_item<T, NC, E, V, SHIFT, VEC>(P, i * V, beta, thresh, mode);
+  if constexpr (V > E) {  // scalar tail: elements the vectors do not cover
+    for (int64_t i = nv * (V / E) + gid; i < n; i += stride)
+      group_shrink_item<T, NC, E, E, SHIFT, false>(P, i * E, beta, thresh,
+                                                   mode);
+  }
+}
+
+template <typename T, bool CPLX, int NC>
+static int group_shrink_launch(void* stream, int mode, void* const* y,
+                               const void* const* a, const void* const* b,
+                               double beta, int64_t n, double thresh) {
+  GroupArgs<T, NC> P;
+  const bool shift = b[0] != nullptr;
+  bool aligned = true;
+  for (int c = 0; c < NC; ++c) {
+    P.y[c] = (T*)y[c];
+    P.a[c] = (const T*)a[c];
+    P.b[c] = shift ? (const T*)b[c] : nullptr;
+    aligned = aligned && ((uintptr_t)y[c] % 16 == 0) &&
+              ((uintptr_t)a[c] % 16 == 0) &&
+              (!shift || (uintptr_t)b[c] % 16 == 0);
+  }
+  constexpr int E = CPLX ? 2 : 1;
+  constexpr int V = VecW<T>::value;
+  hipStream_t s = (hipStream_t)stream;
+  const int64_t grid = grid_1d(aligned ? (n * E) / V + 1 : n);
+#define GROUP_GO(SHIFT, VEC)                                                  \
+  hipLaunchKernelGGL((group_shrink_kernel<T, NC, CPLX, SHIFT, VEC>),          \
+                     dim3(grid), dim3(BLK), 0, s, P, (T)beta, (T)thresh,      \
+                     mode, n)
+  if (shift) {
+    if (aligned) GROUP_GO(true, true);
+    else GROUP_GO(true, false);
+  } else {
+    if (aligned) GROUP_GO(false, true);
+    else GROUP_GO(false, false);
+  }
+#undef GROUP_GO
+  return check(hipGetLastError());
+}
+
+template <typename T, bool CPLX>
+static int group_shrink_nc(void* stream, int mode, int64_t ncomp,
+                           void* const* y, const void* const* a,
+                           const void* const* b, double beta, int64_t n,
+                           double thresh) {
+  switch (ncomp) {
+    case 1: return group_shrink_launch<T, CPLX, 1>(stream, mode, y, a, b, beta, n, thresh);
+    case 2: return group_shrink_launch<T, CPLX, 2>(stream, mode, y, a, b, beta, n, thresh);
+    case 3: return group_shrink_launch<T, CPLX, 3>(stream, mode, y, a, b, beta, n, thresh);
+    default: return group_shrink_launch<T, CPLX, 4>(stream, mode, y, a, b, beta, n, thresh);
+  }
+}
+
+extern "C" int pam_group_shrink(void* stream, int mode, int64_t ncomp,
+                                void* y0, void* y1, void* y2, void* y3,
+                                const void* a0, const void* a1,
+                                const void* a2, const void* a3,
+                                const void* b0, const void* b1,
+                                const void* b2, const void* b3, double beta,
+                                int64_t n, double thresh, int dtype) {
+  void* const y[PAM_GROUP_MAX] = {y0, y1, y2, y3};
+  const void* const a[PAM_GROUP_MAX] = {a0, a1, a2, a3};
+  const void* const b[PAM_GROUP_MAX] = {b0, b1, b2, b3};
+  // every argument check precedes the first HIP call
+  if (ncomp < 1 || ncomp > PAM_GROUP_MAX) return PAM_EARG;
+  for (int64_t c = 0; c < ncomp; ++c) {
+    if (!y[c] || !a[c]) return PAM_EARG;
+    if ((b[c] == nullptr) != (b[0] == nullptr)) return PAM_EARG;
+  }
+  if (n < 0 || !(thresh >= 0.0)) return PAM_EARG;
+  if (mode != 0 && mode != 1) return PAM_EOP;
+  if (dtype < PAM_F64 || dtype > PAM_C64) return PAM_EDTYPE;
+  if (n == 0) return 0;
+  switch (dtype) {
+    case PAM_F64: return group_shrink_nc<double, false>(stream, mode, ncomp, y, a, b, beta, n, thresh);
+    case PAM_F32: return group_shrink_nc<float, false>(stream, mode, ncomp, y, a, b, beta, n, thresh);
+    case PAM_C128: return group_shrink_nc<double, true>(stream, mode, ncomp, y, a, b, beta, n, thresh);
+    default: return group_shrink_nc<float, true>(stream, mode, ncomp, y, a, b, beta, n, thresh);
+  }
+}
+
+// out = sum_i sqrt(sum_c |x_c[i]|^2) in float64: stage 1 is pam_dot's fixed
+// tree (<= NPARTIAL blocks, grid-stride, wave shuffle, LDS), stage 2 the
+// shared deterministic combine.
+template <typename T, int NC>
+struct GroupIn {
+  const T* x[NC];
+};
+
+template <typename T, int NC, bool CPLX>
+__global__ void __launch_bounds__(BLK) group_norm_stage1(
+    GroupIn<T, NC> P, int64_t n, double* __restrict__ partials) {
+  double acc = 0.0;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n;
+       i += stride) {
+    double q = 0.0;
+#pragma unroll
+    for (int c = 0; c < NC; ++c) {
+      if constexpr (CPLX) {
+        const double zr = (double)P.x[c][2 * i];
+        const double zi = (double)P.x[c][2 * i + 1];
+        q += zr * zr + zi * zi;
+      } else {
+        const double xv = (double)P.x[c][i];
+        q += xv * xv;
+      }
+    }
+    acc += sqrt(q);
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off, 64);
+  __shared__ double lds[BLK / 64];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  if (lane == 0) lds[wave] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double r = lds[0];
+#pragma unroll
+    for (int w = 1; w < BLK / 64; ++w) r += lds[w];
+    partials[blockIdx.x] = r;
+  }
+}
+
+template <typename T, bool CPLX, int NC>
+static int group_norm_launch(void* stream, const void* const* x, int64_t n,
+                             void* ws, void* out) {
+  GroupIn<T, NC> P;
+  for (int c = 0; c < NC; ++c) P.x[c] = (const T*)x[c];
+  hipStream_t s = (hipStream_t)stream;
+  int64_t nb = (n + BLK - 1) / BLK;
+  if (nb > NPARTIAL) nb = NPARTIAL;
+  hipLaunchKernelGGL((group_norm_stage1<T, NC, CPLX>), dim3(nb), dim3(BLK), 0,
+                     s, P, n, (double*)ws);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return (int)e;
+  hipLaunchKernelGGL((reduce_stage2<0>), dim3(1), dim3(BLK), 0, s,
+                     (const double*)ws, nb, (double*)out);
+  return check(hipGetLastError());
+}
+
+template <typename T, bool CPLX>
+static int group_norm_nc(void* stream, int64_t ncomp, const void* const* x,
+                         int64_t n, void* ws, void* out) {
+  switch (ncomp) {
+    case 1: return group_norm_launch<T, CPLX, 1>(stream, x, n, ws, out);
+    case 2: return group_norm_launch<T, CPLX, 2>(stream, x, n, ws, out);
+    case 3: return group_norm_launch<T, CPLX, 3>(stream, x, n, ws, out);
+    default: return group_norm_launch<T, CPLX, 4>(stream, x, n, ws, out);
+  }
+}
+
+extern "C" int pam_group_norm(void* stream, int64_t ncomp, const void* x0,
+                              const void* x1, const void* x2, const void* x3,
+                              int64_t n, void* ws, void* out, int dtype) {
+  const void* const x[PAM_GROUP_MAX] = {x0, x1, x2, x3};
+  if (ncomp < 1 || ncomp > PAM_GROUP_MAX) return PAM_EARG;
+  for (int64_t c = 0; c < ncomp; ++c)
+    if (!x[c]) return PAM_EARG;
+  if (n < 0 || !ws || !out) return PAM_EARG;
+  if (dtype < PAM_F64 || dtype > PAM_C64) return PAM_EDTYPE;
+  if (n == 0)  // no launch; stream-ordered, so graph capture stays legal
+    return check(hipMemsetAsync(out, 0, sizeof(double), (hipStream_t)stream));
+  switch (dtype) {
+    case PAM_F64: return group_norm_nc<double, false>(stream, ncomp, x, n, ws, out);
+    case PAM_F32: return group_norm_nc<float, false>(stream, ncomp, x, n, ws, out);
+    case PAM_C128: return group_norm_nc<double, true>(stream, ncomp, x, n, ws, out);
+    default: return group_norm_nc<float, true>(stream, ncomp, x, n, ws, out);
+  }
+}
+
+// ---------------------------------------------------------------------------
 // dense GEMV (local apply of MPIBlockDiag dense operators,
 // ref basicoperators/BlockDiag.py:122-144).  HBM-bound: the matrix read
 // dominates (nr*nc elements, read once).

@@ -193,6 +193,49 @@ def thresh(y, x, kind: int, t: float):  # 0 soft, 1 hard, 2 half; y may be x
     _ew("pam_thresh", y, (x,), post=(int(kind), float(t)), as_real=False)
 
 
+_GROUP_MAX = 4          # PAM_GROUP_MAX pointer slots per operand
+
+
+def _group(name, *seqs):
+    """Component lists of one group launch: each 1 to 4 tensors, equally
+    many, one dtype and one element count -> (ncomp, dtype, n)."""
+    nc = len(seqs[0])
+    if not 1 <= nc <= _GROUP_MAX or any(len(s) != nc for s in seqs):
+        raise ValueError(f"pam: {name}: expected 1 to {_GROUP_MAX} "
+                         f"components per operand, equally many; got "
+                         f"{[len(s) for s in seqs]}")
+    ts = [t for s in seqs for t in s]
+    dtype, n = ts[0].dtype, ts[0].numel()
+    _typed(name, dtype, *ts)
+    _sized(name, n, *ts)
+    return nc, dtype, n
+
+
+def _slots(ts):  # pointers of the components, unused slots NULL
+    return [t.data_ptr() for t in ts] + [None] * (_GROUP_MAX - len(ts))
+
+
+def group_shrink(ys, xs, mode: int, thresh: float, shift=None,
+                 beta: float = 1.0):
+    """ys[c] = v[c] * s with v[c] = xs[c] (+ beta * shift[c]) and s from
+    rho = sqrt(sum_c |v[c]|^2) at each index: mode 0 the L2,1 prox
+    (rho - thresh)_+ / rho, mode 1 the projection min(1, thresh / rho).
+    ys, xs, shift: sequences of 1 to 4 tensors; ys[c] may be xs[c]."""
+    name = "pam_group_shrink"
+    shift = () if shift is None else shift
+    nc, dtype, n = _group(name, ys, xs, *((shift,) if len(shift) else ()))
+    dt = _code(dtype)
+    for y in ys:
+        _dst(name, y)
+    xs = [t.contiguous() for t in xs]
+    shift = [t.contiguous() for t in shift]
+    idx = require_device(*ys, *xs, *shift)
+    if n:
+        _launch(idx, name, (int(mode), nc, *_slots(ys), *_slots(xs),
+                            *_slots(shift), float(beta), n, float(thresh),
+                            dt))
+
+
 def scalar_alpha(out, num, den, damp: float):
     """out[0] = |num[0] / (den[0] + damp * den[1])| on device"""
     name = "pam_scalar_alpha"
@@ -210,9 +253,10 @@ def scalar_div(out, num, den):
 _reduce_scratch = {}    # per device: (ws, out) float64 tensors
 
 
-def _reduce(name, ins, extras, out, nout):
-    """pam_X(stream, *ins, n, *extras, ws, out, dtype) -> out; ``out``
-    None selects the per-device cached result buffer."""
+def _reduce(name, ins, extras, out, nout, pre=(), slots=0):
+    """pam_X(stream, *pre, *ins, n, *extras, ws, out, dtype) -> out;
+    ``out`` None selects the per-device cached result buffer, ``slots``
+    pads the input pointers with NULLs."""
     dtype, n = ins[0].dtype, ins[0].numel()
     _typed(name, dtype, *ins)
     _sized(name, n, *ins)
@@ -227,8 +271,9 @@ def _reduce(name, ins, extras, out, nout):
                                 torch.empty(2, dtype=_F64, device=dev))
     ws, cached = _reduce_scratch[idx]
     out = cached[:nout] if out is None else out
-    _launch(idx, name, (*[t.data_ptr() for t in ins], n, *extras,
-                        ws.data_ptr(), out.data_ptr(), dt))
+    ptrs = [t.data_ptr() for t in ins] + [None] * (slots - len(ins))
+    _launch(idx, name, (*pre, *ptrs, n, *extras, ws.data_ptr(),
+                        out.data_ptr(), dt))
     return out
 
 
@@ -244,6 +289,14 @@ def cdot(x, y, conjx: bool, out=None):
 
 def norm_local(x, op: int, p: float, out=None):  # see pam_norm_local ops
     return _reduce("pam_norm_local", (x,), (int(op), float(p)), out, 1)
+
+
+def group_norm(xs, out=None):
+    """sum_i sqrt(sum_c |xs[c][i]|^2) in float64, xs a sequence of 1 to 4
+    tensors -> 1-element device tensor"""
+    nc, _, _ = _group("pam_group_norm", xs)
+    return _reduce("pam_group_norm", tuple(xs), (), out, 1, pre=(nc,),
+                   slots=_GROUP_MAX)
 
 
 # ------------------------------------------------------- dense GEMV / GEMM

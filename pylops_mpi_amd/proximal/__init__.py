@@ -9,9 +9,9 @@ L1) are restated natively in .operators from pyproximal's published
 definitions and anchored on the reference's own call sites and tests
 (ref tests/test_prox.py, tests/test_proxsolver.py).
 """
-from .operators import (MPIProxOperator, MPIL2,  # noqa: F401
+from .operators import (MPIProxOperator, MPIL2, MPIL21,  # noqa: F401
                         ProxOperator, Box, L0, L1)
 from . import optimization  # noqa: F401
 
-__all__ = ["MPIProxOperator", "MPIL2", "ProxOperator", "Box", "L0", "L1",
-           "optimization"]
+__all__ = ["MPIProxOperator", "MPIL2", "MPIL21", "ProxOperator", "Box", "L0",
+           "L1", "optimization"]

@@ -163,6 +163,82 @@ class MPIProxOperator:
         return y
 
 
+class MPIL21(MPIProxOperator):
+    """sigma * ||x||_{2,1} across the components of a stacked array
+    (pyproximal's L21 with the group axis laid over the stack): the norm
+    at grid point i is taken over (x[0][i], ..., x[ncomp-1][i]) — with x
+    the output of MPIGradient this is isotropic total variation.
+
+    Not separable: it has no local ``proxop`` and is implemented directly
+    on the pam_group_* kernels (include/pam.h), one pass over the 1 to 4
+    components, which must share partition, dtype, mask and the local
+    shapes of every rank.  ``accepts_shift``: prox / proxdual take
+    ``shift=v, beta=b`` and evaluate at ``x + b * v`` in that same pass
+    (the dual update of PrimalDual)."""
+
+    accepts_shift = True
+
+    def __init__(self, sigma: float = 1.0) -> None:
+        self.sigma = float(sigma)
+        self.hasgrad = False
+
+    @staticmethod
+    def _components(x, like=None):
+        """The components' local arrays, validated from what every rank
+        knows (local_shapes), so all ranks raise alike."""
+        if not isinstance(x, StackedDistributedArray):
+            raise TypeError("MPIL21 acts on a StackedDistributedArray, "
+                            f"got {type(x).__name__}")
+        if not 1 <= x.narrays <= kernels._GROUP_MAX:
+            raise ValueError(f"MPIL21 takes 1 to {kernels._GROUP_MAX} "
+                             f"components, got {x.narrays}")
+        first = x[0] if like is None else like[0]
+        if like is not None and like.narrays != x.narrays:
+            raise ValueError("MPIL21: shift has a different number of "
+                             "components")
+        for d in x.distarrays:
+            if d.partition != first.partition or d.dtype != first.dtype \
+                    or d.mask != first.mask \
+                    or d.local_shapes != first.local_shapes:
+                raise ValueError(
+                    "MPIL21: components must share partition, dtype, mask "
+                    f"and local shapes; got {d.partition} {d.dtype} "
+                    f"{d.local_shapes} against {first.partition} "
+                    f"{first.dtype} {first.local_shapes}")
+        return [d.local_array for d in x.distarrays]
+
+    def __call__(self, x) -> float:
+        xs = self._components(x)
+        if xs[0].numel():
+            f = kernels.group_norm(xs)
+        else:
+            # this rank holds no rows: an empty tensor's data_ptr() is
+            # NULL, which pam_group_norm rejects (PAM_EARG) before it
+            # looks at n, so the zero is written here
+            f = torch.zeros(1, dtype=torch.float64, device=xs[0].device)
+        if x[0].partition == Partition.SCATTER:
+            x[0]._sub_comm.allreduce_(f, "sum")
+        return self.sigma * float(f.item())
+
+    def _shrink(self, x, mode, thresh, shift, beta):
+        xs = self._components(x)
+        vs = None if shift is None else self._components(shift, like=x)
+        y = x.empty_like()
+        kernels.group_shrink([d.local_array for d in y.distarrays], xs,
+                             mode, thresh, shift=vs, beta=beta)
+        return y
+
+    def prox(self, x, tau: float, shift=None, beta: float = 1.0,
+             **kwargs: Any):
+        return self._shrink(x, 0, self.sigma * tau, shift, beta)
+
+    def proxdual(self, x, tau: float, shift=None, beta: float = 1.0,
+                 **kwargs: Any):
+        # projection on the per-point ball of radius sigma: the Moreau
+        # dual of prox, independent of the step
+        return self._shrink(x, 1, self.sigma, shift, beta)
+
+
 def _identity_op(x: DistributedArray, dtype):
     """The reference's per-partition identity wrap
     (ref L2.py:149-152,160-163)."""

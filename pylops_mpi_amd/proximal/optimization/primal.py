@@ -7,6 +7,10 @@ Note: the reference accepts `niterback` but its released code never
 branches into backtracking (`tau` is used directly at primal.py:146-149),
 so `tau` is required here too and `niterback` is kept for signature
 parity only.
+
+PrimalDual has no counterpart in the reference: it restates pyproximal's
+published Chambolle-Pock iteration so that a non-separable prox (MPIL21)
+can be used without an inner CGLS solve.
 """
 import sys
 import time
@@ -168,3 +172,86 @@ def ADMML2(
         print("---------------------------------------------------------\n")
         sys.stdout.flush()
     return x, z
+
+
+def PrimalDual(
+    proxf,
+    proxg,
+    A,
+    x0,
+    tau: float,
+    mu: float,
+    y0=None,
+    z=None,
+    theta: float = 1.0,
+    niter: int = 10,
+    gfirst: bool = True,
+    callback: Optional[Callable] = None,
+    returny: bool = False,
+    show: bool = False,
+):
+    """Primal-dual (Chambolle-Pock) iteration for
+    min_x f(x) + z.x + g(A x) — pyproximal's PrimalDual on distributed
+    arrays, fixed steps (convergence needs tau * mu * ||A||^2 < 1).
+
+    ``A`` is an MPILinearOperator or MPIStackedLinearOperator, x and the
+    dual y DistributedArrays or StackedDistributedArrays.  A ``proxg``
+    with ``accepts_shift`` (MPIL21) takes the dual step
+    y <- proxdual(y + mu * A xhat) as one fused pass over y; any other
+    prox object gets the sum formed first.
+    """
+    rank = x0.rank
+    tau, mu, theta = float(tau), float(mu), float(theta)
+    x = x0.copy()
+    xhat = x.copy()
+    # A @ xhat of the first dual step (gfirst), which also gives the
+    # layout of y when there is no y0: one apply serves both
+    Axhat = A @ xhat if gfirst or y0 is None else None
+    y = y0.copy() if y0 is not None else Axhat.zeros_like()
+    fused = getattr(proxg, "accepts_shift", False)
+    if show and rank == 0:
+        tstart = time.time()
+        print("Primal-dual: min_x f(x) + z.x + g(Ax)\n"
+              "---------------------------------------------------------\n"
+              f"Proximal operator (f): {proxf}\n"
+              f"Proximal operator (g): {proxg}\n"
+              f"tau = {tau:10e}\tmu = {mu:10e}\ttheta = {theta:.2f}\t"
+              f"niter = {niter}\n")
+        sys.stdout.flush()
+
+    def dual(y, Axhat):
+        if fused:
+            return proxg.proxdual(y, mu, shift=Axhat, beta=mu)
+        return proxg.proxdual(y + mu * Axhat, mu)
+
+    def primal(x, y):
+        ATy = A.H @ y
+        if z is not None:
+            ATy = ATy + z
+        xnew = proxf.prox(x - tau * ATy, tau)
+        return xnew, xnew + theta * (xnew - x)
+
+    for iiter in range(niter):
+        if gfirst:
+            y = dual(y, Axhat if iiter == 0 else A @ xhat)
+            x, xhat = primal(x, y)
+        else:
+            x, xhat = primal(x, y)
+            y = dual(y, A @ xhat)
+        if callback is not None:
+            callback(x)
+        if show and (iiter < 10 or niter - iiter < 10
+                     or (niter // 10 > 0 and iiter % (niter // 10) == 0)):
+            # the functionals, the operator apply and the dot are
+            # collectives: every rank evaluates them, rank 0 prints
+            pf, pg = proxf(x), proxg(A @ x)
+            pfg = pf + pg if z is None else pf + pg + float(z.dot(x))
+            if rank == 0:
+                print(f"{iiter + 1:6g}  {pf:10.3e}  {pg:10.3e}  "
+                      f"{pfg:10.3e}")
+                sys.stdout.flush()
+    if show and rank == 0:
+        print(f"\nTotal time (s) = {time.time() - tstart:.2f}\n"
+              "---------------------------------------------------------\n")
+        sys.stdout.flush()
+    return (x, y) if returny else x
