@@ -209,6 +209,14 @@ int pam_fd_apply(void* stream, int op, int edge, const void* x,
                  const void* gf, const void* gb, void* y, int64_t nloc,
                  int64_t m, int64_t row0, int64_t nglob, int64_t rbegin,
                  int64_t rend, double coeff, int dtype);
+/* Which kernel pam_fd_apply runs for a launch of nrows = rend - rbegin rows
+ * of m elements (host-side query, no GPU work): 0 row-parallel, 1 rolling
+ * window, 2 row band.  aligned16 != 0 iff x, y and the non-NULL ghost
+ * planes are all 16-byte aligned.  Honours the PAM_FD_* environment
+ * selectors exactly as the launch does (PAM_FD_BAND is re-read per call).
+ * pam_fd_band_rows: output rows per thread of the row-band kernel. */
+int pam_fd_variant(int dtype, int64_t m, int64_t nrows, int aligned16);
+int64_t pam_fd_band_rows(void);
 
 /* Serial non-stationary 1-D convolution along axis d of [batch, d, m]
  * (the local operator of MPINonStationaryConvolve1D's Halo sandwich,

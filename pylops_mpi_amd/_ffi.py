@@ -67,6 +67,8 @@ _SIGS = {
     "pam_nsconv": ([P, I, P, P, P, L, L, L, L, L, D, D, I], I),
     "pam_fd_serial": ([P, I, I, P, P, L, L, L, D, I], I),
     "pam_fd_apply": ([P, I, I, P, P, P, P, L, L, L, L, L, L, D, I], I),
+    "pam_fd_variant": ([I, L, L, I], I),
+    "pam_fd_band_rows": ([], L),
 }
 
 

@@ -1287,32 +1287,91 @@ extern "C" int64_t pam_fd_halo_width(int op) {
   }
 }
 
-template <typename T, int OP, int V, bool NTS = false, bool RSWAP = false>
+// rows from either global end that are NOT interior: some term masked
+// (lo/hi) or touched by fd_edge (which reaches rows 0..2 / N-3..N-1)
+template <int OP>
+constexpr int fd_margin() {
+  int mg = 3;
+  for (int t = 0; t < FDDef<OP>::NT; ++t) {
+    if (FDDef<OP>::TERMS[t].lo > mg) mg = FDDef<OP>::TERMS[t].lo;
+    if (FDDef<OP>::TERMS[t].hi > mg) mg = FDDef<OP>::TERMS[t].hi;
+  }
+  return mg;
+}
+
+// Row-parallel stencil: one block-row per local row, a grid-stride loop
+// over the row's column vectors.  Interior rows — every input row a local
+// row of x, every term active, no edge fixup; uniform per block — take a
+// path with no masks, no fd_edge and no Rows::row select, and with U > 1
+// run U column iterations per trip, all U*NT loads issued before the first
+// store (U*NT 16-B loads in flight per thread instead of NT).  Same
+// arithmetic per output on every path, so the results agree bit for bit.
+template <typename T, int OP, int V, bool NTS = false, int U = 1>
 __global__ void __launch_bounds__(BLK) fd_kernel(Rows<T> R, T* __restrict__ y,
                                                  int64_t row0, int64_t N, T c,
                                                  int edge, int64_t rbegin,
                                                  int64_t rend) {
-  // RSWAP (PAM_FD_RSWAP=1 A/B): row index from blockIdx.x instead of .y,
-  // so XCD round-robin dispatch (linear id mod 8) lands CONSECUTIVE ROWS
-  // on consecutive XCDs instead of consecutive column chunks — probes
-  // whether the long-row deficit is an XCD/L2 block-mapping effect.
-  const int64_t brow = RSWAP ? blockIdx.x : blockIdx.y;
-  const int64_t grows = RSWAP ? gridDim.x : gridDim.y;
-  const int64_t bcol = RSWAP ? blockIdx.y : blockIdx.x;
-  const int64_t gcols = RSWAP ? gridDim.y : gridDim.x;
+  constexpr int W = FDDef<OP>::W, MG = fd_margin<OP>();
+  constexpr int NTm = FDDef<OP>::NT;
+  const int64_t bcol = blockIdx.x;
   const int64_t m = R.m, mv = m / V;
-  const int64_t cstride = (int64_t)gcols * blockDim.x;
-  for (int64_t i = rbegin + brow; i < rend; i += grows) {
+  const int64_t cstride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t i = rbegin + blockIdx.y; i < rend; i += gridDim.y) {
     const int64_t g = row0 + i;
     T* __restrict__ yrow = y + i * m;
-    for (int64_t jv = (int64_t)bcol * blockDim.x + threadIdx.x; jv < mv;
-         jv += cstride) {
+    int64_t jv = (int64_t)bcol * blockDim.x + threadIdx.x;
+    if (i >= W && i + W < R.nloc && g >= MG && g <= N - 1 - MG) {
+      const T* __restrict__ xrow = R.x + i * m;
+      if constexpr (U > 1) {
+        for (; jv + (U - 1) * cstride < mv; jv += U * cstride) {
+          T v[U][NTm][V];
+#pragma unroll
+          for (int u = 0; u < U; ++u)
+#pragma unroll
+            for (int t = 0; t < NTm; ++t)
+              loadv<T, V>(xrow + FDDef<OP>::TERMS[t].off * m +
+                              (jv + u * cstride) * V, v[u][t]);
+#pragma unroll
+          for (int u = 0; u < U; ++u) {
+            T acc[V];
+#pragma unroll
+            for (int k = 0; k < V; ++k) acc[k] = (T)0;
+#pragma unroll
+            for (int t = 0; t < NTm; ++t)
+#pragma unroll
+              for (int k = 0; k < V; ++k)
+                acc[k] += (T)FDDef<OP>::TERMS[t].coeff * v[u][t][k];
+#pragma unroll
+            for (int k = 0; k < V; ++k) acc[k] *= c;
+            storev_p<T, V, NTS>(yrow + (jv + u * cstride) * V, acc);
+          }
+        }
+      }
+      for (; jv < mv; jv += cstride) {
+        const int64_t j = jv * V;
+        T acc[V];
+#pragma unroll
+        for (int k = 0; k < V; ++k) acc[k] = (T)0;
+#pragma unroll
+        for (int t = 0; t < NTm; ++t) {
+          T v[V];
+          loadv<T, V>(xrow + FDDef<OP>::TERMS[t].off * m + j, v);
+#pragma unroll
+          for (int k = 0; k < V; ++k)
+            acc[k] += (T)FDDef<OP>::TERMS[t].coeff * v[k];
+        }
+#pragma unroll
+        for (int k = 0; k < V; ++k) acc[k] *= c;
+        storev_p<T, V, NTS>(yrow + j, acc);
+      }
+    }
+    for (; jv < mv; jv += cstride) {   // edge / ghost rows: masked terms
       const int64_t j = jv * V;
       T acc[V];
 #pragma unroll
       for (int k = 0; k < V; ++k) acc[k] = (T)0;
 #pragma unroll
-      for (int t = 0; t < FDDef<OP>::NT; ++t) {
+      for (int t = 0; t < NTm; ++t) {
         const Term tm = FDDef<OP>::TERMS[t];
         if (g >= tm.lo && g <= N - 1 - tm.hi) {
           T v[V];
@@ -1348,6 +1407,106 @@ __global__ void __launch_bounds__(BLK) fd_kernel(Rows<T> R, T* __restrict__ y,
   }
 }
 
+// Row-band stencil: each thread produces RT consecutive rows of ONE 16-B
+// column vector from RT+2W input rows loaded up front, fully unrolled —
+// (RT+2W loads + RT stores) per RT outputs where fd_kernel issues
+// (2..4 loads + 1 store) per output, RT+2W independent loads in flight per
+// thread, no loop-carried window (fd_roll_kernel) and 1/RT the workgroups.
+// The path is chosen per block from uniform values only:
+//   interior — all RT+2W rows are local rows of x, every row has every
+//     term active and sits outside the rows fd_edge touches: one base
+//     pointer + compile-time multiples of m, no masks / fd_edge / select;
+//   general — everything else (first/last band of the global array, bands
+//     reaching into gf/gb, the partial last band): fd_kernel's per-row
+//     body, row by row, rows >= rend never stored.
+// Per output the arithmetic is fd_kernel's exactly (acc = 0, += coeff*x in
+// TERMS order, *= c), so the two kernels agree bit for bit.
+// RT is compile-time and one value is instantiated: RT = 4 in plain
+// (column blocks, bands) block order is the measured choice among RT in
+// {4, 8, 16} x {plain, 64-column-block panels} (FD paragraph).
+#ifndef PAM_FD_BAND_RT
+#define PAM_FD_BAND_RT 4
+#endif
+
+template <typename T, int OP, int V, int RT, int r, int t>
+__device__ __forceinline__ void band_term(
+    const T (&in)[RT + 2 * FDDef<OP>::W][V], T (&acc)[V]) {
+  constexpr Term tm = FDDef<OP>::TERMS[t];
+#pragma unroll
+  for (int k = 0; k < V; ++k)
+    acc[k] += (T)tm.coeff * in[r + tm.off + FDDef<OP>::W][k];
+}
+
+template <typename T, int OP, int V, int RT, int r, int... Ts>
+__device__ __forceinline__ void band_terms(
+    const T (&in)[RT + 2 * FDDef<OP>::W][V], T (&acc)[V],
+    std::integer_sequence<int, Ts...>) {
+  (band_term<T, OP, V, RT, r, Ts>(in, acc), ...);
+}
+
+template <int... Us, typename F>
+__device__ __forceinline__ void fd_static_for(
+    std::integer_sequence<int, Us...>, F&& f) {
+  (f(std::integral_constant<int, Us>{}), ...);
+}
+
+template <typename T, int OP, int V, int RT>
+__global__ void __launch_bounds__(BLK) fd_band_kernel(
+    Rows<T> R, T* __restrict__ y, int64_t row0, int64_t N, T c, int edge,
+    int64_t rbegin, int64_t rend, uint32_t ncb) {
+  constexpr int W = FDDef<OP>::W;
+  constexpr int MG = fd_margin<OP>();
+  // 1-D grid, column blocks fastest: a band sweeps its rows end to end
+  const uint32_t band = blockIdx.x / ncb, cb = blockIdx.x - band * ncb;
+  const int64_t m = R.m;
+  const int64_t jv = (int64_t)cb * BLK + threadIdx.x;
+  if (jv >= m / V) return;
+  const int64_t j = jv * V;
+  const int64_t i0 = rbegin + (int64_t)band * RT;
+  const int64_t g0 = row0 + i0;
+  const bool interior = i0 - W >= 0 && i0 + RT - 1 + W < R.nloc &&
+                        i0 + RT <= rend && g0 >= MG &&
+                        g0 + RT - 1 <= N - 1 - MG;
+  if (interior) {
+    const T* __restrict__ p = R.x + (i0 - W) * m + j;
+    T in[RT + 2 * W][V];
+#pragma unroll
+    for (int k = 0; k < RT + 2 * W; ++k) loadv<T, V>(p + k * m, in[k]);
+    T* __restrict__ q = y + i0 * m + j;
+    fd_static_for(std::make_integer_sequence<int, RT>{}, [&](auto rc) {
+      constexpr int r = decltype(rc)::value;
+      T acc[V];
+#pragma unroll
+      for (int k = 0; k < V; ++k) acc[k] = (T)0;
+      band_terms<T, OP, V, RT, r>(
+          in, acc, std::make_integer_sequence<int, FDDef<OP>::NT>{});
+#pragma unroll
+      for (int k = 0; k < V; ++k) acc[k] *= c;
+      storev<T, V>(q + r * m, acc);
+    });
+    return;
+  }
+  for (int64_t i = i0; i < i0 + RT && i < rend; ++i) {
+    const int64_t g = row0 + i;
+    T acc[V];
+#pragma unroll
+    for (int k = 0; k < V; ++k) acc[k] = (T)0;
+#pragma unroll
+    for (int t = 0; t < FDDef<OP>::NT; ++t) {
+      const Term tm = FDDef<OP>::TERMS[t];
+      if (g >= tm.lo && g <= N - 1 - tm.hi) {
+        T v[V];
+        loadv<T, V>(R.row(i + tm.off) + j, v);
+#pragma unroll
+        for (int k = 0; k < V; ++k) acc[k] += (T)tm.coeff * v[k];
+      }
+    }
+    if (edge) fd_edge<T, OP, V>(R, i, j, g, N, acc);
+#pragma unroll
+    for (int k = 0; k < V; ++k) acc[k] *= c;
+    storev<T, V>(y + i * m + j, acc);
+  }
+}
 
 // constexpr-folded term accumulation for the rolling window: `tm` is a
 // constexpr LOCAL here, so buf[tm.off + W] is a CONSTANT register index
@@ -1464,111 +1623,6 @@ __global__ void __launch_bounds__(BLK) fd_roll_kernel(
   }
 }
 
-template <int... Us, typename F>
-__device__ __forceinline__ void fd_static_for(
-    std::integer_sequence<int, Us...>, F&& f) {
-  (f(std::integral_constant<int, Us>{}), ...);
-}
-
-// roll2 term accumulation: window slot is ((off + W + ROT) mod NROLL) —
-// all constexpr, so the window lives in registers with NO per-row shift
-template <typename T, int OP, int V, int W, int ROT, int t>
-__device__ __forceinline__ void roll2_term(const T (&win)[2 * W + 1][V],
-                                           T (&acc)[V], int64_t g,
-                                           int64_t N) {
-  constexpr Term tm = FDDef<OP>::TERMS[t];
-  constexpr int NR = 2 * W + 1;
-  constexpr int slot = ((tm.off + W + ROT) % NR + NR) % NR;
-  if (g >= tm.lo && g <= N - 1 - tm.hi) {
-#pragma unroll
-    for (int k = 0; k < V; ++k)
-      acc[k] += (T)tm.coeff * win[slot][k];
-  }
-}
-
-template <typename T, int OP, int V, int W, int ROT, int... Ts>
-__device__ __forceinline__ void roll2_terms(
-    const T (&win)[2 * W + 1][V], T (&acc)[V], int64_t g, int64_t N,
-    std::integer_sequence<int, Ts...>) {
-  (roll2_term<T, OP, V, W, ROT, Ts>(win, acc, g, N), ...);
-}
-
-// Statically-rotated rolling stencil (PAM_FD_ROLL=2, r02): like
-// fd_roll_kernel (1 load + 1 store per point — the PMC-measured fix for
-// the long-row shape, where the row-parallel kernel's neighbour re-read
-// really does go to HBM: FETCH 8.53 GB vs 4.29 algorithmic at
-// 512x4096x256, r02 session 1), but the row loop is unrolled by the
-// window depth so the slot indices rotate at COMPILE time — no
-// register-to-register window shift per row (fd_roll_kernel spends
-// 2W*V*CV moves per row step; this kernel spends zero).  Loads for row
-// i+W+1 issue before row i's arithmetic, giving CV independent loads
-// in flight per thread.
-template <typename T, int OP, int V, int CV, bool NTS = false>
-__global__ void __launch_bounds__(BLK) fd_roll2_kernel(
-    Rows<T> R, T* __restrict__ y, int64_t row0, int64_t N, T c, int edge,
-    int64_t rbegin, int64_t rend) {
-  constexpr int W = FDDef<OP>::W;
-  constexpr int NROLL = 2 * W + 1;
-  const int64_t m = R.m, mv = m / V;
-  const int64_t base = (int64_t)blockIdx.x * blockDim.x * CV + threadIdx.x;
-  const int64_t nr = rend - rbegin;
-  const int64_t c0 = rbegin + (nr * blockIdx.y) / gridDim.y;
-  const int64_t c1 = rbegin + (nr * (blockIdx.y + 1)) / gridDim.y;
-  if (c1 <= c0 || base >= mv) return;
-  const int64_t lo = R.gf ? -(int64_t)R.w : 0;
-  const int64_t hi = R.nloc - 1 + (R.gb ? R.w : 0);
-  auto clamp_row = [&](int64_t i) {
-    return i < lo ? lo : (i > hi ? hi : i);
-  };
-  int64_t js[CV];
-  bool vq[CV];
-#pragma unroll
-  for (int q = 0; q < CV; ++q) {
-    const int64_t jq = base + (int64_t)q * blockDim.x;
-    vq[q] = jq < mv;
-    js[q] = (vq[q] ? jq : mv - 1) * V;
-  }
-  T buf[CV][NROLL][V];
-#pragma unroll
-  for (int q = 0; q < CV; ++q)
-#pragma unroll
-    for (int k = 0; k < NROLL; ++k)
-      loadv<T, V>(R.row(clamp_row(c0 - W + k)) + js[q], buf[q][k]);
-  int64_t i = c0;
-  auto step = [&](auto rotc) {
-    constexpr int ROT = decltype(rotc)::value;
-    constexpr int oldest = ROT % NROLL;
-    const int64_t rn = clamp_row(i + W + 1);
-    T nxt[CV][V];
-#pragma unroll
-    for (int q = 0; q < CV; ++q)
-      loadv<T, V>(R.row(rn) + js[q], nxt[q]);
-    const int64_t g = row0 + i;
-#pragma unroll
-    for (int q = 0; q < CV; ++q) {
-      T acc[V];
-#pragma unroll
-      for (int k = 0; k < V; ++k) acc[k] = (T)0;
-      roll2_terms<T, OP, V, W, ROT>(
-          buf[q], acc, g, N,
-          std::make_integer_sequence<int, FDDef<OP>::NT>{});
-      if (edge) fd_edge<T, OP, V>(R, i, js[q], g, N, acc);
-#pragma unroll
-      for (int k = 0; k < V; ++k) acc[k] *= c;
-      if (vq[q]) storev_p<T, V, NTS>(y + i * m + js[q], acc);
-#pragma unroll
-      for (int v = 0; v < V; ++v) buf[q][oldest][v] = nxt[q][v];
-    }
-    ++i;
-  };
-  while (i + NROLL <= c1)
-    fd_static_for(std::make_integer_sequence<int, NROLL>{},
-                  [&](auto rc) { step(rc); });
-  fd_static_for(std::make_integer_sequence<int, NROLL>{}, [&](auto rc) {
-    if (i < c1) step(rc);
-  });
-}
-
 static int fd_vec_override() {
   static int v = [] {
     const char* e = getenv("PAM_FD_VEC");
@@ -1591,6 +1645,81 @@ static int fd_nt_override() {
   return v;
 }
 
+static int fd_roll_override() {
+  static int v = [] {
+    const char* e = getenv("PAM_FD_ROLL");
+    return e ? atoi(e) : 0;
+  }();
+  return v;
+}
+
+static int64_t fd_longrow() {
+  static int64_t v = [] {
+    const char* e = getenv("PAM_FD_LONGROW");
+    return (int64_t)(e ? atoll(e) : (4 << 20));
+  }();
+  return v;
+}
+
+// per-lane vector width of the row-parallel kernel.  default: 16 B/lane
+// (double2 / float4) — the measured optimum; 32 B (V=4 double) was -14%
+// in an A/B (PAM_FD_VEC keeps the knob)
+static int fd_vec_width(int tsize, int64_t m, bool align16) {
+  if (!align16) return 1;
+  const int vw = 16 / tsize;
+  int V = (m % vw == 0) ? vw : 1;
+  const int ov = fd_vec_override();
+  if ((ov == 1 || ov == 2 || ov == 4) && m % ov == 0) V = ov;
+  return V;
+}
+
+// AUTO rule of the band kernel (measured, DESIGN.md FD paragraph): it
+// takes the mid-size ragged branch of the rolling rule — rows of 5/8..1x
+// PAM_FD_LONGROW (2.5-4 MiB) with nrows % 1024 != 0 — where it measures
+// 5.84 TB/s against the rolling kernel's 5.59 at (1536, 1536x256).  It
+// loses to the row-parallel kernel at the bench shape and to the rolling
+// kernel above 4 MiB rows, so those keep their kernels.  Floor: fewer than
+// 4 bands of rows (the overlap path's 1-2-row boundary launches) stay
+// where they were.
+static bool fd_band_auto(int64_t rowbytes, int64_t nrows, int64_t longrow) {
+  return rowbytes <= longrow && rowbytes * 8 >= longrow * 5 &&
+         (nrows % 1024) != 0 && nrows >= 4 * PAM_FD_BAND_RT;
+}
+
+// Which kernel serves a launch of nrows = rend - rbegin rows of m elements
+// of tsize bytes: 0 row-parallel (fd_kernel), 1 rolling (fd_roll_kernel),
+// 2 row band (fd_band_kernel).  Pure host; fd_launch dispatches on it and
+// pam_fd_variant exports it.  PAM_FD_BAND is read on EVERY call (tests flip
+// it in-process): unset = auto, 1 = band wherever eligible (16-B lanes,
+// any nrows >= 1), -1 = never.
+static int fd_variant(int tsize, int64_t m, int64_t nrows, bool align16) {
+  const int V = fd_vec_width(tsize, m, align16);
+  const bool band_ok = V > 1 && V == 16 / tsize;
+  const char* e = getenv("PAM_FD_BAND");
+  const int bandov = e ? atoi(e) : 0;
+  if (bandov > 0 && band_ok && nrows >= 1) return 2;
+  const int rollov = fd_roll_override();
+  const int64_t rowbytes = m * (int64_t)tsize;
+  const int64_t longrow = fd_longrow();
+  const bool roll_shape =
+      rowbytes > longrow ||
+      (rowbytes * 8 >= longrow * 5 && (nrows % 1024) != 0);
+  if (bandov == 0 && rollov == 0 && band_ok &&
+      fd_band_auto(rowbytes, nrows, longrow))
+    return 2;
+  if (V > 1 && (rollov > 0 || (rollov == 0 && roll_shape))) return 1;
+  return 0;
+}
+
+extern "C" int pam_fd_variant(int dtype, int64_t m, int64_t nrows,
+                              int aligned16) {
+  if (dtype != PAM_F64 && dtype != PAM_F32) return PAM_EDTYPE;
+  if (m <= 0 || nrows < 0) return PAM_EARG;
+  return fd_variant(dtype == PAM_F64 ? 8 : 4, m, nrows, aligned16 != 0);
+}
+
+extern "C" int64_t pam_fd_band_rows(void) { return PAM_FD_BAND_RT; }
+
 template <typename T, int OP>
 static int fd_launch(void* stream, int edge, const void* x, const void* gf,
                      const void* gb, void* y, int64_t nloc, int64_t m,
@@ -1603,16 +1732,19 @@ static int fd_launch(void* stream, int edge, const void* x, const void* gf,
   const bool align16 = ((uintptr_t)x % 16 == 0) && ((uintptr_t)y % 16 == 0) &&
                        (gf == nullptr || (uintptr_t)gf % 16 == 0) &&
                        (gb == nullptr || (uintptr_t)gb % 16 == 0);
-  // default: 16 B/lane (double2 / float4) — the measured optimum; 32 B
-  // (V=4 double) was -14% in an A/B (PAM_FD_VEC keeps the knob)
-  int V = 1;
-  if (align16) {
-    if (sizeof(T) == 8)
-      V = (m % 2 == 0) ? 2 : 1;
-    else
-      V = (m % 4 == 0) ? 4 : 1;
-    const int ov = fd_vec_override();
-    if ((ov == 1 || ov == 2 || ov == 4) && m % ov == 0) V = ov;
+  int V = fd_vec_width((int)sizeof(T), m, align16);
+  const int variant = fd_variant((int)sizeof(T), m, nrows, align16);
+  hipStream_t s = (hipStream_t)stream;
+  if (variant == 2) {
+    constexpr int BV = VecW<T>::value, RT = PAM_FD_BAND_RT;
+    const int64_t ncb = (m / BV + BLK - 1) / BLK;
+    const int64_t nbands = (nrows + RT - 1) / RT;
+    if (ncb * nbands > 0x7fffffffLL) return PAM_EARG;
+    hipLaunchKernelGGL((fd_band_kernel<T, OP, BV, RT>),
+                       dim3((uint32_t)(ncb * nbands)), dim3(BLK), 0, s, R,
+                       (T*)y, row0, nglob, (T)coeff, edge, rbegin, rend,
+                       (uint32_t)ncb);
+    return check(hipGetLastError());
   }
   const int64_t mv = m / V;
   // Grid shape (PAM_FD_GY / PAM_FD_CAP override for A/Bs): one block-row
@@ -1638,7 +1770,6 @@ static int fd_launch(void* stream, int edge, const void* x, const void* gf,
   if (cap < 1) cap = 1;
   if (gx64 > cap) gx64 = cap;
   dim3 grid((uint32_t)gx64, (uint32_t)gy);
-  hipStream_t s = (hipStream_t)stream;
   // rolling-window path: DEFAULT for long rows (r02).  r01's negative
   // A/B predates the constexpr-folded window; the r02 PMC runs show the
   // row-parallel kernel's neighbour-row re-reads really go to HBM once
@@ -1648,8 +1779,9 @@ static int fd_launch(void* stream, int edge, const void* x, const void* gf,
   // V=4/CV=8/TGT=2048 (the swept optimum; NT stores -15%, roll2's
   // static rotation spills at CV8V4).  The bench shape (2 MiB rows)
   // keeps the row-parallel kernel (5.78 vs 5.22).  PAM_FD_ROLL: unset =
-  // auto, -1 = force row-parallel, 1/2 = force rolling (2 = the
-  // statically-rotated variant).  The r02s10/s11 12-shape crossover
+  // auto, -1 = force row-parallel, > 0 = force rolling (the statically-
+  // rotated variant that 2 used to select is gone: DESIGN.md, negative
+  // results).  The r02s10/s11 12-shape crossover
   // sweep (profiles/) refined the auto rule: the rolling kernel is
   // flat (~5.0-5.3 TB/s) while row-parallel is peaky (4.8-5.7), and
   // row-parallel loses not only above 4 MiB rows but ALSO at mid-size
@@ -1660,24 +1792,14 @@ static int fd_launch(void* stream, int edge, const void* x, const void* gf,
   // rowbytes > PAM_FD_LONGROW (default 4 MiB, strict — the 4 MiB
   // power-of-two shape prefers row-parallel), or when rowbytes >=
   // 5/8 of it (2.5 MiB) and nrows % 1024 != 0.
-  static int rollov = [] {
-    const char* e = getenv("PAM_FD_ROLL");
-    return e ? atoi(e) : 0;
-  }();
-  static int64_t longrow = [] {
-    const char* e = getenv("PAM_FD_LONGROW");
-    return (int64_t)(e ? atoll(e) : (4 << 20));
-  }();
-  const int64_t rowbytes = m * (int64_t)sizeof(T);
-  const bool roll_auto =
-      rollov == 0 && V > 1 &&
-      (rowbytes > longrow ||
-       (rowbytes * 8 >= longrow * 5 && (nrows % 1024) != 0));
+  // The rule itself lives in fd_variant.
+  const int rollov = fd_roll_override();
+  const bool roll_auto = rollov == 0 && variant == 1;
   static int rolltgt = [] {
     const char* e = getenv("PAM_FD_ROLL_TGT");
     return e ? atoi(e) : 2048;
   }();
-  if ((rollov > 0 && V > 1) || roll_auto) {
+  if (variant == 1) {
     // upgrade to 32-B lanes for the rolling form (its swept optimum;
     // the row-parallel kernel's optimum stays 16 B)
     if (roll_auto && fd_vec_override() == 0 && m % 4 == 0 && align16)
@@ -1722,45 +1844,14 @@ static int fd_launch(void* stream, int edge, const void* x, const void* gf,
     else                                                                      \
       ROLL_LAUNCH(fd_roll_kernel, VV, CC);                                    \
   } while (0)
-    if (rollov == 2) {        // statically-rotated variant
-      if (V == 4 && CV == 2) ROLL_LAUNCH(fd_roll2_kernel, 4, 2);
-      else if (V == 4 && CV == 8) ROLL_LAUNCH(fd_roll2_kernel, 4, 8);
-      else if (V == 4) ROLL_LAUNCH(fd_roll2_kernel, 4, 4);
-      else if (CV == 2) ROLL_LAUNCH(fd_roll2_kernel, 2, 2);
-      else if (CV == 8) ROLL_LAUNCH(fd_roll2_kernel, 2, 8);
-      else ROLL_LAUNCH(fd_roll2_kernel, 2, 4);
-    } else {
-      if (V == 4 && CV == 2) ROLL_LAUNCH1(4, 2);
-      else if (V == 4 && CV == 8) ROLL_LAUNCH1(4, 8);
-      else if (V == 4) ROLL_LAUNCH1(4, 4);
-      else if (CV == 2) ROLL_LAUNCH1(2, 2);
-      else if (CV == 8) ROLL_LAUNCH1(2, 8);
-      else ROLL_LAUNCH1(2, 4);
-    }
+    if (V == 4 && CV == 2) ROLL_LAUNCH1(4, 2);
+    else if (V == 4 && CV == 8) ROLL_LAUNCH1(4, 8);
+    else if (V == 4) ROLL_LAUNCH1(4, 4);
+    else if (CV == 2) ROLL_LAUNCH1(2, 2);
+    else if (CV == 8) ROLL_LAUNCH1(2, 8);
+    else ROLL_LAUNCH1(2, 4);
 #undef ROLL_LAUNCH1
 #undef ROLL_LAUNCH
-    return check(hipGetLastError());
-  }
-  // PAM_FD_RSWAP=1: row index from blockIdx.x (XCD-mapping A/B; see
-  // fd_kernel docstring).  Grid dims swap with it.
-  static int rswap = [] {
-    const char* e = getenv("PAM_FD_RSWAP");
-    return e ? atoi(e) : 0;
-  }();
-  if (rswap) {
-    dim3 grid_s((uint32_t)gy, (uint32_t)gx64);
-    if (V == 4)
-      hipLaunchKernelGGL((fd_kernel<T, OP, 4, false, true>), grid_s,
-                         dim3(BLK), 0, s, R, (T*)y, row0, nglob, (T)coeff,
-                         edge, rbegin, rend);
-    else if (V == 2 && sizeof(T) == 8)
-      hipLaunchKernelGGL((fd_kernel<T, OP, 2, false, true>), grid_s,
-                         dim3(BLK), 0, s, R, (T*)y, row0, nglob, (T)coeff,
-                         edge, rbegin, rend);
-    else
-      hipLaunchKernelGGL((fd_kernel<T, OP, 1, false, true>), grid_s,
-                         dim3(BLK), 0, s, R, (T*)y, row0, nglob, (T)coeff,
-                         edge, rbegin, rend);
     return check(hipGetLastError());
   }
   const bool nt = fd_nt_override() != 0;
@@ -1774,7 +1865,16 @@ static int fd_launch(void* stream, int edge, const void* x, const void* gf,
     else
       hipLaunchKernelGGL((fd_kernel<T, OP, 1, true>), grid, dim3(BLK), 0, s,
                          R, (T*)y, row0, nglob, (T)coeff, edge, rbegin, rend);
-  } else if (V == 4)
+  } else if (V == VecW<T>::value && (mv + BLK - 1) / BLK >= 4 * gx64)
+    // >= 4 column iterations per block at 16-B lanes (every large launch:
+    // the grid cap above sets ~4): the 4x-unrolled interior path.  At the
+    // bench shape 5.87 -> 6.10 TB/s, the interior path alone 5.97; with a
+    // single iteration per block the unrolled kernel is slower than the
+    // plain one (4.3 vs 5.9 TB/s at 64 rows), so it is not used there.
+    hipLaunchKernelGGL((fd_kernel<T, OP, VecW<T>::value, false, 4>), grid,
+                       dim3(BLK), 0, s, R, (T*)y, row0, nglob, (T)coeff, edge,
+                       rbegin, rend);
+  else if (V == 4)
     hipLaunchKernelGGL((fd_kernel<T, OP, 4>), grid, dim3(BLK), 0, s, R, (T*)y,
                        row0, nglob, (T)coeff, edge, rbegin, rend);
   else if (V == 2 && sizeof(T) == 8)

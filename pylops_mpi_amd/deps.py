@@ -17,8 +17,23 @@ pylops_mpi/utils/deps.py:58-66 (NCCL_PYLOPS_MPI / PYLOPS_MPI_CUDA_AWARE):
                           use the 1-load/pt rolling kernel — the r02
                           long-row fix, 4.85 -> 5.35 TB/s at the N=8
                           per-rank shape); -1 = force row-parallel;
-                          1/2 = force rolling (2 = statically-rotated
-                          variant, measured slower at CV8xV4)
+                          > 0 = force rolling (the statically-rotated
+                          variant 2 used to select spilled at CV8xV4 and
+                          was removed, as was the PAM_FD_RSWAP block
+                          mapping, -18% at the bench shape)
+  PAM_FD_BAND             row-band stencil select (RT rows of one 16-B
+                          column vector per thread, RT+2W loads up front):
+                          unset = AUTO, 1 = band wherever eligible (16-B
+                          lanes; any row count), -1 = never.  Read on every
+                          launch, so it can be flipped in-process;
+                          kernels.fd_variant reports the kernel a launch
+                          will use.  AUTO picks it where it measured
+                          faster: 2.5-4 MiB rows with a row count that is
+                          no multiple of 1024 and >= 16 (5.63 vs the
+                          rolling kernel's 5.34 TB/s at 1536x1536x256); it
+                          lost to the row-parallel kernel at the bench
+                          shape and to the rolling kernel above 4 MiB rows
+                          (DESIGN.md)
   PAM_FD_ROLL_CV / PAM_FD_ROLL_TGT  rolling chains per thread (default
                           8) and target grid size (default 2048) — the
                           r02 swept optima

@@ -442,6 +442,29 @@ def fd_apply(y, x, gf, gb, op: int, edge: bool, row0: int, nglob: int,
         int(row0), int(nglob), int(rbegin), int(rend), float(coeff), dt))
 
 
+FD_ROW, FD_ROLL, FD_BAND = 0, 1, 2  # pam_fd_variant codes
+
+
+def fd_band_rows() -> int:  # output rows per thread of the row-band kernel
+    return int(_ffi.lib().pam_fd_band_rows())
+
+
+def fd_variant(y, x, gf, gb, rbegin: int, rend: int) -> int:
+    """The kernel fd_apply(y, x, gf, gb, ..., rbegin, rend, ...) runs with
+    the environment as it is now: FD_ROW, FD_ROLL or FD_BAND.  Host-side
+    query; nothing is enqueued."""
+    k, dt = _real_code(y)
+    x, gf, gb = (t if t is None else t.contiguous() for t in (x, gf, gb))
+    aligned = all(t.data_ptr() % 16 == 0 for t in (y, x, gf, gb)
+                  if t is not None)
+    v = int(_ffi.lib().pam_fd_variant(dt, k * x.shape[1],
+                                      int(rend) - int(rbegin),
+                                      1 if aligned else 0))
+    if v < 0:
+        _ffi.checked(v, "pam_fd_variant")
+    return v
+
+
 def fd_serial(y, x, op: int, edge: bool, coeff: float):
     """Stencil ``op`` along dim 1 of the [batch, d, m] block ``x``.
     Complex blocks run as their real view with doubled m."""
