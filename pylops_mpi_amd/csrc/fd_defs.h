@@ -1,11 +1,14 @@
-// fd_defs.h — shared finite-difference stencil tables, halo accessor and
-// edge fixups used by both the distributed (pam.hip) and serial
+// fd_defs.h — shared finite-difference stencil tables, halo accessor, row
+// bodies and edge fixups used by both the distributed (pam.hip) and serial
 // (fdserial.hip) kernels.  See pam.hip header comment for design notes.
 #ifndef PAM_FD_DEFS_H
 #define PAM_FD_DEFS_H
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <utility>
+
+#include "../../include/pam.h"
 
 template <typename T> struct VecW;                // 16-B vector width per T
 template <> struct VecW<double> { static constexpr int value = 2; };
@@ -13,10 +16,12 @@ template <> struct VecW<float> { static constexpr int value = 4; };
 
 template <typename T, int V> struct VecT;
 template <> struct VecT<double, 2> { using type = double2; };
-template <> struct VecT<double, 4> { using type = double4; };
-template <> struct VecT<float, 2> { using type = float2; };
 template <> struct VecT<float, 4> { using type = float4; };
 
+// Plain loads and stores only: nt stores, nt loads and forced lane widths
+// all measured no-change or negative on the stencils and are not in the
+// build (DESIGN.md "Negative results kept", scripts/probe_nt_store.hip,
+// profiles/r02_fd_sweep_session*.log).
 template <typename T, int V>
 __device__ __forceinline__ void loadv(const T* __restrict__ p, T* v) {
   if constexpr (V == 1) {
@@ -38,24 +43,6 @@ __device__ __forceinline__ void loadv(const T* __restrict__ p, T* v) {
       v[2] = t.z;
       v[3] = t.w;
     }
-  }
-}
-
-// nontemporal-load variant (TH_NT): the rolling stencil reads every
-// input element exactly once, so L2 allocation on its loads is pure
-// overhead — A/B'd via PAM_FD_NTL (r02).
-template <typename T, int V>
-__device__ __forceinline__ void loadv_nt(const T* __restrict__ p, T* v) {
-  if constexpr (V == 1) {
-    v[0] = __builtin_nontemporal_load(p);
-  } else if constexpr (sizeof(T) == 8 && V == 4) {
-    v[0] = __builtin_nontemporal_load(p);
-    v[1] = __builtin_nontemporal_load(p + 1);
-    v[2] = __builtin_nontemporal_load(p + 2);
-    v[3] = __builtin_nontemporal_load(p + 3);
-  } else {
-#pragma unroll
-    for (int k = 0; k < V; ++k) v[k] = __builtin_nontemporal_load(p + k);
   }
 }
 
@@ -84,45 +71,17 @@ __device__ __forceinline__ void storev(T* __restrict__ p, const T* v) {
   }
 }
 
-// non-temporal (nt cache hint) store for the streaming stencil output.
-// Measured (r01): +9% in the standalone probe (scripts/probe_nt_store.hip,
-// weak launch geometry) but NO change on the production kernel, which is
-// already at the read+write mix ceiling — kept behind PAM_FD_NT=1 as a
-// documented negative; nt LOADS are -25% (row re-use lives in L2).
-typedef double __attribute__((ext_vector_type(2))) ntv_d2;
-typedef float __attribute__((ext_vector_type(4))) ntv_f4;
-template <typename T> struct NtVec;
-template <> struct NtVec<double> { using type = ntv_d2; static constexpr int W = 2; };
-template <> struct NtVec<float> { using type = ntv_f4; static constexpr int W = 4; };
-
-template <typename T, int V>
-__device__ __forceinline__ void storev_nt(T* __restrict__ p, const T* v) {
-  if constexpr (V < NtVec<T>::W) {  // incl. V==1 and PAM_FD_VEC=2 float
-#pragma unroll
-    for (int k = 0; k < V; ++k) __builtin_nontemporal_store(v[k], p + k);
-  } else {
-    // 16-B native-vector nt stores (clang ext_vector: the builtin rejects
-    // HIP_vector_type)
-    using VT = typename NtVec<T>::type;
-    constexpr int W = NtVec<T>::W;
-#pragma unroll
-    for (int c = 0; c < V / W; ++c) {
-      VT t;
-#pragma unroll
-      for (int k = 0; k < W; ++k) t[k] = v[c * W + k];
-      __builtin_nontemporal_store(t, reinterpret_cast<VT*>(p) + c);
-    }
-  }
+// f(std::integral_constant<int, 0>{}) ... f(std::integral_constant<int,
+// N-1>{}), in order: a loop whose index is a compile-time constant inside f.
+template <typename F, int... Is>
+__host__ __device__ __forceinline__ void fd_unroll_seq(
+    F&& f, std::integer_sequence<int, Is...>) {
+  (f(std::integral_constant<int, Is>{}), ...);
 }
-
-template <typename T, int V, bool NT>
-__device__ __forceinline__ void storev_p(T* __restrict__ p, const T* v) {
-  if constexpr (NT)
-    storev_nt<T, V>(p, v);
-  else
-    storev<T, V>(p, v);
+template <int N, typename F>
+__host__ __device__ __forceinline__ void fd_unroll(F&& f) {
+  fd_unroll_seq(f, std::make_integer_sequence<int, N>{});
 }
-
 
 struct Term {
   int off;       // row offset of the input sample
@@ -222,6 +181,18 @@ template <> struct FDDef<13> {
                                      {0, -2.0, 1, 1},
                                      {-1, 1.0, 2, 0}};
 };
+
+// Host-side op-code dispatch: returns f(std::integral_constant<int, OP>{})
+// for op == OP in [0, FD_NOPS), PAM_EOP otherwise.
+constexpr int FD_NOPS = 14;
+template <typename F>
+static inline int fd_dispatch_op(int op, F&& f) {
+  int rc = PAM_EOP;
+  fd_unroll<FD_NOPS>([&](auto opc) {
+    if (op == decltype(opc)::value) rc = f(opc);
+  });
+  return rc;
+}
 
 
 template <typename T>
@@ -337,6 +308,71 @@ __device__ __forceinline__ void fd_edge(const Rows<T>& R, int64_t i, int64_t j,
       for (int k = 0; k < V; ++k) acc[k] += u[k];
     }
   }
+}
+
+// The two row bodies every pam.hip stencil kernel is made of.  Both compute
+// acc = 0, acc += coeff * x in TERMS order, acc *= c last — the same
+// roundings per output, which is why the kernels agree bit for bit.
+
+// Masked body, any row: V outputs of local row i (global row g) at column j
+// go to yrow + j, yrow the output row (block-uniform, so the per-thread
+// address is formed at the store, after the loads).  Terms outside their
+// global-row interval are skipped, inputs come through Rows::row (local or
+// halo plane), fd_edge applies under edge.
+template <typename T, int OP, int V>
+__device__ __forceinline__ void fd_row_masked(const Rows<T>& R, int64_t i,
+                                              int64_t j, int64_t g, int64_t N,
+                                              T c, int edge, T* yrow) {
+  T acc[V];
+#pragma unroll
+  for (int k = 0; k < V; ++k) acc[k] = (T)0;
+#pragma unroll
+  for (int t = 0; t < FDDef<OP>::NT; ++t) {
+    const Term tm = FDDef<OP>::TERMS[t];
+    if (g >= tm.lo && g <= N - 1 - tm.hi) {
+      T v[V];
+      loadv<T, V>(R.row(i + tm.off) + j, v);
+#pragma unroll
+      for (int k = 0; k < V; ++k) acc[k] += (T)tm.coeff * v[k];
+    }
+  }
+  if (edge) fd_edge<T, OP, V>(R, i, j, g, N, acc);
+#pragma unroll
+  for (int k = 0; k < V; ++k) acc[k] *= c;
+  storev<T, V>(yrow + j, acc);
+}
+
+// Unmasked interior body on rows already in registers: output row r of the
+// window, stored at dst + r * m; win[k] holds input row k - W, every term is
+// active.  The window index is a compile-time constant per term (constexpr
+// tm); a runtime-indexed window goes to scratch.
+template <typename T, int OP, int V, int NR, int r = 0>
+__device__ __forceinline__ void fd_row_interior(const T (&win)[NR][V], T c,
+                                                T* dst, int64_t m) {
+  T acc[V];
+#pragma unroll
+  for (int k = 0; k < V; ++k) acc[k] = (T)0;
+  fd_unroll<FDDef<OP>::NT>([&](auto tc) {
+    constexpr Term tm = FDDef<OP>::TERMS[decltype(tc)::value];
+#pragma unroll
+    for (int k = 0; k < V; ++k)
+      acc[k] += (T)tm.coeff * win[r + tm.off + FDDef<OP>::W][k];
+  });
+#pragma unroll
+  for (int k = 0; k < V; ++k) acc[k] *= c;
+  storev<T, V>(dst + r * m, acc);
+}
+
+// The rows fd_row_interior reads, loaded from p = &x[row][j] of the output
+// row: one load per term, in TERMS order; window rows no term uses stay
+// unloaded and unread.
+template <typename T, int OP, int V>
+__device__ __forceinline__ void fd_load_terms(
+    const T* __restrict__ p, int64_t m, T (&win)[2 * FDDef<OP>::W + 1][V]) {
+  fd_unroll<FDDef<OP>::NT>([&](auto tc) {
+    constexpr Term tm = FDDef<OP>::TERMS[decltype(tc)::value];
+    loadv<T, V>(p + tm.off * m, win[tm.off + FDDef<OP>::W]);
+  });
 }
 
 

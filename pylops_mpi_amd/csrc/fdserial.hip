@@ -109,28 +109,15 @@ static int fd_serial_launch(void* stream, int edge, const void* x, void* y,
 extern "C" int pam_fd_serial(void* stream, int op, int edge, const void* x,
                              void* y, int64_t batch, int64_t d, int64_t m,
                              double coeff, int dtype) {
-#define FDS_CASE(T)                                                           \
-  switch (op) {                                                               \
-    case 0: return fd_serial_launch<T, 0>(stream, edge, x, y, batch, d, m, coeff); \
-    case 1: return fd_serial_launch<T, 1>(stream, edge, x, y, batch, d, m, coeff); \
-    case 2: return fd_serial_launch<T, 2>(stream, edge, x, y, batch, d, m, coeff); \
-    case 3: return fd_serial_launch<T, 3>(stream, edge, x, y, batch, d, m, coeff); \
-    case 4: return fd_serial_launch<T, 4>(stream, edge, x, y, batch, d, m, coeff); \
-    case 5: return fd_serial_launch<T, 5>(stream, edge, x, y, batch, d, m, coeff); \
-    case 6: return fd_serial_launch<T, 6>(stream, edge, x, y, batch, d, m, coeff); \
-    case 7: return fd_serial_launch<T, 7>(stream, edge, x, y, batch, d, m, coeff); \
-    case 8: return fd_serial_launch<T, 8>(stream, edge, x, y, batch, d, m, coeff); \
-    case 9: return fd_serial_launch<T, 9>(stream, edge, x, y, batch, d, m, coeff); \
-    case 10: return fd_serial_launch<T, 10>(stream, edge, x, y, batch, d, m, coeff); \
-    case 11: return fd_serial_launch<T, 11>(stream, edge, x, y, batch, d, m, coeff); \
-    case 12: return fd_serial_launch<T, 12>(stream, edge, x, y, batch, d, m, coeff); \
-    case 13: return fd_serial_launch<T, 13>(stream, edge, x, y, batch, d, m, coeff); \
-    default: return PAM_EOP;                                                  \
-  }
-  if (dtype == PAM_F64) { FDS_CASE(double) }
-  if (dtype == PAM_F32) { FDS_CASE(float) }
-#undef FDS_CASE
-  return PAM_EDTYPE;
+  if (dtype != PAM_F64 && dtype != PAM_F32) return PAM_EDTYPE;
+  return fd_dispatch_op(op, [&](auto opc) {
+    constexpr int OP = decltype(opc)::value;
+    return dtype == PAM_F64
+               ? fd_serial_launch<double, OP>(stream, edge, x, y, batch, d, m,
+                                              coeff)
+               : fd_serial_launch<float, OP>(stream, edge, x, y, batch, d, m,
+                                             coeff);
+  });
 }
 
 

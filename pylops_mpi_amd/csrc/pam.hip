@@ -1,11 +1,12 @@
 // pam — pylops-mpi hot path, MI355X-native (gfx950/CDNA4) kernels.
 //
-// Design notes (see also /root/repo/DESIGN.md):
+// Design notes:
 //  * Every kernel is HBM-bound (stencils: 16 B/pt algorithmic fp64;
-//    axpy: 24 B/pt; dot: 16 B/pt).  They are written as coalesced
-//    grid-stride loops with 16-byte vector accesses (double2 / float4),
-//    block = 256 threads (4 waves of 64), grids capped so blocks ≫ 256 CUs
-//    but bounded (Guideline 11).
+//    axpy: 24 B/pt; dot: 16 B/pt): coalesced 16-byte vector accesses
+//    (double2 / float4), block = 256 threads (4 waves of 64).  Launch
+//    shapes differ by family: element-wise kernels run one block per 256
+//    vector items with no stride loop (grid_1d), reductions a fixed grid of
+//    at most NPARTIAL grid-stride blocks, stencils the grid fd_plan picks.
 //  * The finite-difference stencils are FUSED: one pass, reading the
 //    neighbour halo planes directly from small exchange buffers instead of
 //    materializing a concatenated ghosted copy the way the reference does
@@ -638,6 +639,27 @@ template <int RED> __device__ __forceinline__ double red_init() {
   else return 0.0;
 }
 
+// The fixed tail of every deterministic reduction: 64-lane __shfl_down per
+// wave -> one LDS slot per wave -> thread 0 combines the BLK/64 slots in
+// order.  The result is valid in thread 0 only.  All calls in one kernel
+// share the LDS slots: a second call needs a __syncthreads() before it.
+template <int RED>
+__device__ __forceinline__ double block_reduce(double acc) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1)
+    acc = red_combine<RED>(acc, __shfl_down(acc, off, 64));
+  __shared__ double lds[BLK / 64];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  if (lane == 0) lds[wave] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    acc = lds[0];
+#pragma unroll
+    for (int w = 1; w < BLK / 64; ++w) acc = red_combine<RED>(acc, lds[w]);
+  }
+  return acc;
+}
+
 template <typename T, int RED, bool CPLX = false>
 __global__ void __launch_bounds__(BLK) reduce_stage1(
     const T* __restrict__ x, const T* __restrict__ y, int64_t n, double p,
@@ -674,20 +696,8 @@ __global__ void __launch_bounds__(BLK) reduce_stage1(
     }
     acc = red_combine<RED>(acc, v);
   }
-  // 64-lane wavefront shuffle reduction
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1)
-    acc = red_combine<RED>(acc, __shfl_down(acc, off, 64));
-  __shared__ double lds[BLK / 64];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  if (lane == 0) lds[wave] = acc;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double r = lds[0];
-#pragma unroll
-    for (int w = 1; w < BLK / 64; ++w) r = red_combine<RED>(r, lds[w]);
-    partials[blockIdx.x] = r;
-  }
+  const double r = block_reduce<RED>(acc);
+  if (threadIdx.x == 0) partials[blockIdx.x] = r;
 }
 
 template <int RED>
@@ -696,19 +706,8 @@ __global__ void __launch_bounds__(BLK) reduce_stage2(
   double acc = red_init<RED>();
   for (int64_t i = threadIdx.x; i < np; i += BLK)
     acc = red_combine<RED>(acc, partials[i]);
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1)
-    acc = red_combine<RED>(acc, __shfl_down(acc, off, 64));
-  __shared__ double lds[BLK / 64];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  if (lane == 0) lds[wave] = acc;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double r = lds[0];
-#pragma unroll
-    for (int w = 1; w < BLK / 64; ++w) r = red_combine<RED>(r, lds[w]);
-    *out = r;
-  }
+  const double r = block_reduce<RED>(acc);
+  if (threadIdx.x == 0) *out = r;
 }
 
 template <typename T, int RED, bool CPLX = false>
@@ -748,25 +747,10 @@ __global__ void __launch_bounds__(BLK) cdot_stage1(
     ar += xr * yr - xi * yi;
     ai += xr * yi + xi * yr;
   }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    ar += __shfl_down(ar, off, 64);
-    ai += __shfl_down(ai, off, 64);
-  }
-  __shared__ double lr[BLK / 64], li[BLK / 64];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  if (lane == 0) {
-    lr[wave] = ar;
-    li[wave] = ai;
-  }
+  const double sr = block_reduce<0>(ar);
   __syncthreads();
+  const double si = block_reduce<0>(ai);
   if (threadIdx.x == 0) {
-    double sr = lr[0], si = li[0];
-#pragma unroll
-    for (int w = 1; w < BLK / 64; ++w) {
-      sr += lr[w];
-      si += li[w];
-    }
     pre[blockIdx.x] = sr;
     pim[blockIdx.x] = si;
   }
@@ -780,25 +764,10 @@ __global__ void __launch_bounds__(BLK) cdot_stage2(
     ar += pre[i];
     ai += pim[i];
   }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    ar += __shfl_down(ar, off, 64);
-    ai += __shfl_down(ai, off, 64);
-  }
-  __shared__ double lr[BLK / 64], li[BLK / 64];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  if (lane == 0) {
-    lr[wave] = ar;
-    li[wave] = ai;
-  }
+  const double sr = block_reduce<0>(ar);
   __syncthreads();
+  const double si = block_reduce<0>(ai);
   if (threadIdx.x == 0) {
-    double sr = lr[0], si = li[0];
-#pragma unroll
-    for (int w = 1; w < BLK / 64; ++w) {
-      sr += lr[w];
-      si += li[w];
-    }
     out[0] = sr;
     out[1] = si;
   }
@@ -1084,18 +1053,8 @@ __global__ void __launch_bounds__(BLK) group_norm_stage1(
     }
     acc += sqrt(q);
   }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off, 64);
-  __shared__ double lds[BLK / 64];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  if (lane == 0) lds[wave] = acc;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double r = lds[0];
-#pragma unroll
-    for (int w = 1; w < BLK / 64; ++w) r += lds[w];
-    partials[blockIdx.x] = r;
-  }
+  const double r = block_reduce<0>(acc);
+  if (threadIdx.x == 0) partials[blockIdx.x] = r;
 }
 
 template <typename T, bool CPLX, int NC>
@@ -1276,6 +1235,11 @@ extern "C" int pam_gemv(void* stream, int trans, const void* A, const void* x,
 // fused finite-difference stencils
 // (ref FirstDerivative.py:141-318, SecondDerivative.py:124-256 — closed
 //  forms of the slice algebra; masks are global-row intervals)
+//
+// Three kernels, one arithmetic (fd_defs.h fd_row_masked / fd_row_interior),
+// chosen per launch by fd_plan: row-parallel (fd_kernel), rolling window
+// (fd_roll_kernel, long rows) and row band (fd_band_kernel, mid-size ragged
+// shapes).  Measurements behind the rules: DESIGN.md §3 and §8.
 // ---------------------------------------------------------------------------
 
 extern "C" int64_t pam_fd_halo_width(int op) {
@@ -1299,20 +1263,37 @@ constexpr int fd_margin() {
   return mg;
 }
 
+// Interior column trips of one row: U column vectors per trip while U fit,
+// all U*NT loads issued before the first store (U*NT 16-B loads in flight
+// per thread instead of NT).  Advances jv past what it stored.
+template <typename T, int OP, int V, int U>
+__device__ __forceinline__ void fd_interior_trips(
+    const T* __restrict__ xrow, T* __restrict__ yrow, int64_t m, int64_t mv,
+    int64_t cstride, T c, int64_t& jv) {
+  constexpr int NR = 2 * FDDef<OP>::W + 1;
+  for (; jv + (U - 1) * cstride < mv; jv += U * cstride) {
+    T win[U][NR][V];
+#pragma unroll
+    for (int u = 0; u < U; ++u)
+      fd_load_terms<T, OP, V>(xrow + (jv + u * cstride) * V, m, win[u]);
+#pragma unroll
+    for (int u = 0; u < U; ++u)
+      fd_row_interior<T, OP, V, NR>(win[u], c, yrow + (jv + u * cstride) * V,
+                                    m);
+  }
+}
+
 // Row-parallel stencil: one block-row per local row, a grid-stride loop
 // over the row's column vectors.  Interior rows — every input row a local
-// row of x, every term active, no edge fixup; uniform per block — take a
-// path with no masks, no fd_edge and no Rows::row select, and with U > 1
-// run U column iterations per trip, all U*NT loads issued before the first
-// store (U*NT 16-B loads in flight per thread instead of NT).  Same
-// arithmetic per output on every path, so the results agree bit for bit.
-template <typename T, int OP, int V, bool NTS = false, int U = 1>
+// row of x, every term active, no edge fixup; uniform per block — take the
+// unmasked trips (U per trip, then singly); every other row, and the columns
+// the trips left, take the masked body.
+template <typename T, int OP, int V, int U>
 __global__ void __launch_bounds__(BLK) fd_kernel(Rows<T> R, T* __restrict__ y,
                                                  int64_t row0, int64_t N, T c,
                                                  int edge, int64_t rbegin,
                                                  int64_t rend) {
   constexpr int W = FDDef<OP>::W, MG = fd_margin<OP>();
-  constexpr int NTm = FDDef<OP>::NT;
   const int64_t bcol = blockIdx.x;
   const int64_t m = R.m, mv = m / V;
   const int64_t cstride = (int64_t)gridDim.x * blockDim.x;
@@ -1322,87 +1303,17 @@ __global__ void __launch_bounds__(BLK) fd_kernel(Rows<T> R, T* __restrict__ y,
     int64_t jv = (int64_t)bcol * blockDim.x + threadIdx.x;
     if (i >= W && i + W < R.nloc && g >= MG && g <= N - 1 - MG) {
       const T* __restrict__ xrow = R.x + i * m;
-      if constexpr (U > 1) {
-        for (; jv + (U - 1) * cstride < mv; jv += U * cstride) {
-          T v[U][NTm][V];
-#pragma unroll
-          for (int u = 0; u < U; ++u)
-#pragma unroll
-            for (int t = 0; t < NTm; ++t)
-              loadv<T, V>(xrow + FDDef<OP>::TERMS[t].off * m +
-                              (jv + u * cstride) * V, v[u][t]);
-#pragma unroll
-          for (int u = 0; u < U; ++u) {
-            T acc[V];
-#pragma unroll
-            for (int k = 0; k < V; ++k) acc[k] = (T)0;
-#pragma unroll
-            for (int t = 0; t < NTm; ++t)
-#pragma unroll
-              for (int k = 0; k < V; ++k)
-                acc[k] += (T)FDDef<OP>::TERMS[t].coeff * v[u][t][k];
-#pragma unroll
-            for (int k = 0; k < V; ++k) acc[k] *= c;
-            storev_p<T, V, NTS>(yrow + (jv + u * cstride) * V, acc);
-          }
-        }
-      }
-      for (; jv < mv; jv += cstride) {
-        const int64_t j = jv * V;
-        T acc[V];
-#pragma unroll
-        for (int k = 0; k < V; ++k) acc[k] = (T)0;
-#pragma unroll
-        for (int t = 0; t < NTm; ++t) {
-          T v[V];
-          loadv<T, V>(xrow + FDDef<OP>::TERMS[t].off * m + j, v);
-#pragma unroll
-          for (int k = 0; k < V; ++k)
-            acc[k] += (T)FDDef<OP>::TERMS[t].coeff * v[k];
-        }
-#pragma unroll
-        for (int k = 0; k < V; ++k) acc[k] *= c;
-        storev_p<T, V, NTS>(yrow + j, acc);
-      }
+      if constexpr (U > 1)
+        fd_interior_trips<T, OP, V, U>(xrow, yrow, m, mv, cstride, c, jv);
+      fd_interior_trips<T, OP, V, 1>(xrow, yrow, m, mv, cstride, c, jv);
     }
-    for (; jv < mv; jv += cstride) {   // edge / ghost rows: masked terms
-      const int64_t j = jv * V;
-      T acc[V];
-#pragma unroll
-      for (int k = 0; k < V; ++k) acc[k] = (T)0;
-#pragma unroll
-      for (int t = 0; t < NTm; ++t) {
-        const Term tm = FDDef<OP>::TERMS[t];
-        if (g >= tm.lo && g <= N - 1 - tm.hi) {
-          T v[V];
-          loadv<T, V>(R.row(i + tm.off) + j, v);
-#pragma unroll
-          for (int k = 0; k < V; ++k) acc[k] += (T)tm.coeff * v[k];
-        }
-      }
-      if (edge) fd_edge<T, OP, V>(R, i, j, g, N, acc);
-#pragma unroll
-      for (int k = 0; k < V; ++k) acc[k] *= c;
-      storev_p<T, V, NTS>(yrow + j, acc);
-    }
+    for (; jv < mv; jv += cstride)
+      fd_row_masked<T, OP, V>(R, i, jv * V, g, N, c, edge, yrow);
     // scalar tail columns (m not divisible by V)
     if constexpr (V > 1) {
       for (int64_t j = mv * V + (int64_t)bcol * blockDim.x + threadIdx.x;
-           j < m; j += cstride) {
-        T acc[1] = {(T)0};
-#pragma unroll
-        for (int t = 0; t < FDDef<OP>::NT; ++t) {
-          const Term tm = FDDef<OP>::TERMS[t];
-          if (g >= tm.lo && g <= N - 1 - tm.hi)
-            acc[0] += (T)tm.coeff * R.row(i + tm.off)[j];
-        }
-        if (edge) fd_edge<T, OP, 1>(R, i, j, g, N, acc);
-        const T o = acc[0] * c;
-        if constexpr (NTS)
-          __builtin_nontemporal_store(o, yrow + j);
-        else
-          yrow[j] = o;
-      }
+           j < m; j += cstride)
+        fd_row_masked<T, OP, 1>(R, i, j, g, N, c, edge, yrow);
     }
   }
 }
@@ -1415,40 +1326,14 @@ __global__ void __launch_bounds__(BLK) fd_kernel(Rows<T> R, T* __restrict__ y,
 // The path is chosen per block from uniform values only:
 //   interior — all RT+2W rows are local rows of x, every row has every
 //     term active and sits outside the rows fd_edge touches: one base
-//     pointer + compile-time multiples of m, no masks / fd_edge / select;
+//     pointer + compile-time multiples of m, the unmasked body per row;
 //   general — everything else (first/last band of the global array, bands
-//     reaching into gf/gb, the partial last band): fd_kernel's per-row
-//     body, row by row, rows >= rend never stored.
-// Per output the arithmetic is fd_kernel's exactly (acc = 0, += coeff*x in
-// TERMS order, *= c), so the two kernels agree bit for bit.
-// RT is compile-time and one value is instantiated: RT = 4 in plain
-// (column blocks, bands) block order is the measured choice among RT in
-// {4, 8, 16} x {plain, 64-column-block panels} (FD paragraph).
+//     reaching into gf/gb, the partial last band): the masked body, row by
+//     row, rows >= rend never stored.
+// RT is compile-time and one value is instantiated (choice: DESIGN.md §3).
 #ifndef PAM_FD_BAND_RT
 #define PAM_FD_BAND_RT 4
 #endif
-
-template <typename T, int OP, int V, int RT, int r, int t>
-__device__ __forceinline__ void band_term(
-    const T (&in)[RT + 2 * FDDef<OP>::W][V], T (&acc)[V]) {
-  constexpr Term tm = FDDef<OP>::TERMS[t];
-#pragma unroll
-  for (int k = 0; k < V; ++k)
-    acc[k] += (T)tm.coeff * in[r + tm.off + FDDef<OP>::W][k];
-}
-
-template <typename T, int OP, int V, int RT, int r, int... Ts>
-__device__ __forceinline__ void band_terms(
-    const T (&in)[RT + 2 * FDDef<OP>::W][V], T (&acc)[V],
-    std::integer_sequence<int, Ts...>) {
-  (band_term<T, OP, V, RT, r, Ts>(in, acc), ...);
-}
-
-template <int... Us, typename F>
-__device__ __forceinline__ void fd_static_for(
-    std::integer_sequence<int, Us...>, F&& f) {
-  (f(std::integral_constant<int, Us>{}), ...);
-}
 
 template <typename T, int OP, int V, int RT>
 __global__ void __launch_bounds__(BLK) fd_band_kernel(
@@ -1473,98 +1358,54 @@ __global__ void __launch_bounds__(BLK) fd_band_kernel(
 #pragma unroll
     for (int k = 0; k < RT + 2 * W; ++k) loadv<T, V>(p + k * m, in[k]);
     T* __restrict__ q = y + i0 * m + j;
-    fd_static_for(std::make_integer_sequence<int, RT>{}, [&](auto rc) {
+    fd_unroll<RT>([&](auto rc) {
       constexpr int r = decltype(rc)::value;
-      T acc[V];
-#pragma unroll
-      for (int k = 0; k < V; ++k) acc[k] = (T)0;
-      band_terms<T, OP, V, RT, r>(
-          in, acc, std::make_integer_sequence<int, FDDef<OP>::NT>{});
-#pragma unroll
-      for (int k = 0; k < V; ++k) acc[k] *= c;
-      storev<T, V>(q + r * m, acc);
+      fd_row_interior<T, OP, V, RT + 2 * W, r>(in, c, q, m);
     });
     return;
   }
-  for (int64_t i = i0; i < i0 + RT && i < rend; ++i) {
-    const int64_t g = row0 + i;
-    T acc[V];
+  for (int64_t i = i0; i < i0 + RT && i < rend; ++i)
+    fd_row_masked<T, OP, V>(R, i, j, row0 + i, N, c, edge, y + i * m);
+}
+
+// Rolling-window stencil: each block walks a row range carrying the 2W+1
+// input rows of its column vectors in registers, so every x element is
+// loaded from HBM exactly once — the row-parallel kernel relies on L2
+// absorbing its neighbour-row re-reads, which fades once a row outgrows it.
+// CV independent column vectors per thread (separate windows) give CV
+// outstanding loads per row step; a single chain is latency-bound (one
+// dependent load per row).  Chains are BLOCK-interleaved (chain q of lane t
+// at column block*BLK*CV + q*BLK + t) so each chain's wave accesses stay
+// coalesced.  CV = 8 is the swept optimum.
+// Guards: load indices are clamped to existing rows (halo planes included)
+// and columns; term/edge masks ignore the clamped garbage and an invalid
+// chain stores nothing.
+#define PAM_FD_ROLL_CV 8
+
+// masked accumulate over the window win[k] = row i-W+k.  The window index
+// is a compile-time constant per term: with a runtime index the windows go
+// to scratch (measured 2.0 TB/s instead of 5.2).
+template <typename T, int OP, int V>
+__device__ __forceinline__ void roll_terms(
+    const T (&win)[2 * FDDef<OP>::W + 1][V], T (&acc)[V], int64_t g,
+    int64_t N) {
+  fd_unroll<FDDef<OP>::NT>([&](auto tc) {
+    constexpr Term tm = FDDef<OP>::TERMS[decltype(tc)::value];
+    if (g >= tm.lo && g <= N - 1 - tm.hi) {
 #pragma unroll
-    for (int k = 0; k < V; ++k) acc[k] = (T)0;
-#pragma unroll
-    for (int t = 0; t < FDDef<OP>::NT; ++t) {
-      const Term tm = FDDef<OP>::TERMS[t];
-      if (g >= tm.lo && g <= N - 1 - tm.hi) {
-        T v[V];
-        loadv<T, V>(R.row(i + tm.off) + j, v);
-#pragma unroll
-        for (int k = 0; k < V; ++k) acc[k] += (T)tm.coeff * v[k];
-      }
+      for (int k = 0; k < V; ++k)
+        acc[k] += (T)tm.coeff * win[tm.off + FDDef<OP>::W][k];
     }
-    if (edge) fd_edge<T, OP, V>(R, i, j, g, N, acc);
-#pragma unroll
-    for (int k = 0; k < V; ++k) acc[k] *= c;
-    storev<T, V>(y + i * m + j, acc);
-  }
+  });
 }
 
-// constexpr-folded term accumulation for the rolling window: `tm` is a
-// constexpr LOCAL here, so buf[tm.off + W] is a CONSTANT register index
-// (the plain `for (t) { Term tm = TERMS[t]; buf[tm.off+W] }` form keeps
-// the window in scratch — measured 2.0 TB/s vs in-register)
-template <typename T, int OP, int V, int W, int t>
-__device__ __forceinline__ void roll_term(const T (&win)[2 * W + 1][V],
-                                          T (&acc)[V], int64_t g,
-                                          int64_t N) {
-  constexpr Term tm = FDDef<OP>::TERMS[t];
-  if (g >= tm.lo && g <= N - 1 - tm.hi) {
-#pragma unroll
-    for (int k = 0; k < V; ++k)
-      acc[k] += (T)tm.coeff * win[tm.off + W][k];
-  }
-}
-
-template <typename T, int OP, int V, int W, int... Ts>
-__device__ __forceinline__ void roll_terms(const T (&win)[2 * W + 1][V],
-                                           T (&acc)[V], int64_t g,
-                                           int64_t N,
-                                           std::integer_sequence<int, Ts...>) {
-  (roll_term<T, OP, V, W, Ts>(win, acc, g, N), ...);
-}
-
-// Rolling-window stencil (EXPERIMENTAL, PAM_FD_ROLL=1; r01 status
-// below): each block walks a row range carrying the 2W+1 input rows in
-// registers — every x element loaded from HBM exactly once, where the
-// row-parallel fd_kernel relies on L2 absorbing neighbour-row re-reads
-// (which fades at long rows: the (512,4096,256) N=8 per-rank shape
-// measures 4.9 TB/s row-parallel vs 5.7 at the bench shape; a pad/
-// non-pow2 probe — scripts/probe_rowstride.hip — ruled out row-stride
-// channel aliasing, leaving re-read absorption as the cause).
-// r01 measurements of THIS kernel: single chain/thread 4.8-5.2 TB/s;
-// CV=4 chains with a runtime-indexed window spilled to scratch
-// (~2.0 TB/s); with the constexpr-folded roll_terms below the window
-// stays in registers and CV=4 reaches 4.9 (long rows) / 5.2 (bench
-// shape) TB/s — STILL below the row-parallel kernel (4.9 / 5.7).  Key
-// datum: rolling reads each x element exactly once, so its 4.9 TB/s on
-// the long-row shape is a TRUE 16 B/pt streaming rate — the long-row
-// gap is therefore NOT neighbour-row re-read traffic; something about
-// the 1-load+1-store-per-row-step pattern (vs axpy's 5.78 on the same
-// mix) is the round-2 question.
-// Guards: load indices are clamped to existing rows (halo planes
-// included); term/edge masks ignore the clamped garbage.
-template <typename T, int OP, int V, int CV, bool NTS = false,
-          bool NTL = false>
+template <typename T, int OP, int V>
 __global__ void __launch_bounds__(BLK) fd_roll_kernel(
     Rows<T> R, T* __restrict__ y, int64_t row0, int64_t N, T c, int edge,
     int64_t rbegin, int64_t rend) {
-  constexpr int W = FDDef<OP>::W;
+  constexpr int W = FDDef<OP>::W, CV = PAM_FD_ROLL_CV;
   constexpr int NROLL = 2 * W + 1;
   const int64_t m = R.m, mv = m / V;
-  // CV independent column-vectors per thread (separate rolling windows)
-  // => CV outstanding loads per row step instead of 1: the single-chain
-  // form was memory-latency-bound (one dependent load per row).  Chains
-  // are BLOCK-interleaved (chain q of lane t at column block*BLK*CV +
-  // q*BLK + t) so each chain's wave accesses stay fully coalesced.
   const int64_t base = (int64_t)blockIdx.x * blockDim.x * CV + threadIdx.x;
   const int64_t nr = rend - rbegin;
   const int64_t c0 = rbegin + (nr * blockIdx.y) / gridDim.y;
@@ -1590,29 +1431,24 @@ __global__ void __launch_bounds__(BLK) fd_roll_kernel(
   for (int q = 0; q < CV; ++q)
 #pragma unroll
     for (int k = 0; k < NROLL; ++k)
-      if constexpr (NTL) loadv_nt<T, V>(R.row(clamp_row(c0 - W + k)) + js[q], buf[q][k]);
-      else loadv<T, V>(R.row(clamp_row(c0 - W + k)) + js[q], buf[q][k]);
+      loadv<T, V>(R.row(clamp_row(c0 - W + k)) + js[q], buf[q][k]);
   for (int64_t i = c0; i < c1; ++i) {
     const int64_t g = row0 + i;
     // issue ALL next-row loads first (CV independent chains)
     T nxt[CV][V];
     const int64_t rn = clamp_row(i + 1 + W);
 #pragma unroll
-    for (int q = 0; q < CV; ++q)
-      if constexpr (NTL) loadv_nt<T, V>(R.row(rn) + js[q], nxt[q]);
-      else loadv<T, V>(R.row(rn) + js[q], nxt[q]);
+    for (int q = 0; q < CV; ++q) loadv<T, V>(R.row(rn) + js[q], nxt[q]);
 #pragma unroll
     for (int q = 0; q < CV; ++q) {
       T acc[V];
 #pragma unroll
       for (int k = 0; k < V; ++k) acc[k] = (T)0;
-      roll_terms<T, OP, V, W>(
-          buf[q], acc, g, N,
-          std::make_integer_sequence<int, FDDef<OP>::NT>{});
+      roll_terms<T, OP, V>(buf[q], acc, g, N);
       if (edge) fd_edge<T, OP, V>(R, i, js[q], g, N, acc);
 #pragma unroll
       for (int k = 0; k < V; ++k) acc[k] *= c;
-      if (vq[q]) storev_p<T, V, NTS>(y + i * m + js[q], acc);
+      if (vq[q]) storev<T, V>(y + i * m + js[q], acc);
 #pragma unroll
       for (int k = 0; k < NROLL - 1; ++k)
 #pragma unroll
@@ -1623,102 +1459,141 @@ __global__ void __launch_bounds__(BLK) fd_roll_kernel(
   }
 }
 
-static int fd_vec_override() {
-  static int v = [] {
-    const char* e = getenv("PAM_FD_VEC");
-    return e ? atoi(e) : 0;
-  }();
-  return v;
+// ---- launch plan: which kernel, which lane width, which grid -------------
+
+static int64_t fd_env(const char* name, int64_t dflt) {
+  const char* e = getenv(name);
+  return e ? atoll(e) : dflt;
 }
 
-// PAM_FD_NT=1 opts the output stores into the nt cache hint.  Measured
-// NEGATIVE on the production kernel (bench A/B r01: 291.2 plain vs 290.5
-// nt pairs/s — no change): the +9% the standalone probe saw
-// (scripts/probe_nt_store.hip) does not transfer once the launch geometry
-// gives the row re-use its L2 locality; the kernel is already at the
-// platform's read+write mix ceiling.  Default: plain stores.
-static int fd_nt_override() {
-  static int v = [] {
-    const char* e = getenv("PAM_FD_NT");
-    return e ? atoi(e) : 0;
-  }();
-  return v;
-}
+enum { FD_ROW = 0, FD_ROLL = 1, FD_BAND = 2 };  // pam_fd_variant's codes
 
-static int fd_roll_override() {
-  static int v = [] {
-    const char* e = getenv("PAM_FD_ROLL");
-    return e ? atoi(e) : 0;
-  }();
-  return v;
-}
+struct FdPlan {
+  int variant;     // FD_ROW / FD_ROLL / FD_BAND
+  int V;           // elements per lane the launch really uses
+  bool u4;         // FD_ROW: the 4x-unrolled interior trips
+  int64_t gx, gy;  // grid; FD_BAND: column blocks x bands, launched 1-D
+};
 
-static int64_t fd_longrow() {
-  static int64_t v = [] {
-    const char* e = getenv("PAM_FD_LONGROW");
-    return (int64_t)(e ? atoll(e) : (4 << 20));
-  }();
-  return v;
-}
-
-// per-lane vector width of the row-parallel kernel.  default: 16 B/lane
-// (double2 / float4) — the measured optimum; 32 B (V=4 double) was -14%
-// in an A/B (PAM_FD_VEC keeps the knob)
-static int fd_vec_width(int tsize, int64_t m, bool align16) {
-  if (!align16) return 1;
+// The launch of nrows = rend - rbegin rows of m elements of tsize bytes.
+// Pure host: fd_launch dispatches on it and pam_fd_variant reports it.
+//   PAM_FD_BAND  (read on EVERY call, tests flip it in-process) unset =
+//                auto, 1 = band wherever eligible, -1 = never
+//   PAM_FD_ROLL  unset = auto, -1 = never rolling, > 0 = rolling wherever
+//                eligible;  PAM_FD_LONGROW  the long-row threshold, bytes
+//   PAM_FD_GY / PAM_FD_CAP  row-parallel grid caps;  PAM_FD_ROLL_TGT
+//                rolling target block count
+// Every kernel but the V = 1 row-parallel one needs 16-B lanes: 16-B
+// aligned pointers and m a multiple of 16 / tsize.
+static FdPlan fd_plan(int tsize, int64_t m, int64_t nrows, bool align16) {
+  static const int64_t rollov = fd_env("PAM_FD_ROLL", 0);
+  static const int64_t longrow = fd_env("PAM_FD_LONGROW", 4 << 20);
+  static const int64_t gycap = fd_env("PAM_FD_GY", 65535);
+  static const int64_t totcap = fd_env("PAM_FD_CAP", 262144);
+  static const int64_t rolltgt = fd_env("PAM_FD_ROLL_TGT", 2048);
+  const int64_t bandov = fd_env("PAM_FD_BAND", 0);
   const int vw = 16 / tsize;
-  int V = (m % vw == 0) ? vw : 1;
-  const int ov = fd_vec_override();
-  if ((ov == 1 || ov == 2 || ov == 4) && m % ov == 0) V = ov;
-  return V;
-}
-
-// AUTO rule of the band kernel (measured, DESIGN.md FD paragraph): it
-// takes the mid-size ragged branch of the rolling rule — rows of 5/8..1x
-// PAM_FD_LONGROW (2.5-4 MiB) with nrows % 1024 != 0 — where it measures
-// 5.84 TB/s against the rolling kernel's 5.59 at (1536, 1536x256).  It
-// loses to the row-parallel kernel at the bench shape and to the rolling
-// kernel above 4 MiB rows, so those keep their kernels.  Floor: fewer than
-// 4 bands of rows (the overlap path's 1-2-row boundary launches) stay
-// where they were.
-static bool fd_band_auto(int64_t rowbytes, int64_t nrows, int64_t longrow) {
-  return rowbytes <= longrow && rowbytes * 8 >= longrow * 5 &&
-         (nrows % 1024) != 0 && nrows >= 4 * PAM_FD_BAND_RT;
-}
-
-// Which kernel serves a launch of nrows = rend - rbegin rows of m elements
-// of tsize bytes: 0 row-parallel (fd_kernel), 1 rolling (fd_roll_kernel),
-// 2 row band (fd_band_kernel).  Pure host; fd_launch dispatches on it and
-// pam_fd_variant exports it.  PAM_FD_BAND is read on EVERY call (tests flip
-// it in-process): unset = auto, 1 = band wherever eligible (16-B lanes,
-// any nrows >= 1), -1 = never.
-static int fd_variant(int tsize, int64_t m, int64_t nrows, bool align16) {
-  const int V = fd_vec_width(tsize, m, align16);
-  const bool band_ok = V > 1 && V == 16 / tsize;
-  const char* e = getenv("PAM_FD_BAND");
-  const int bandov = e ? atoi(e) : 0;
-  if (bandov > 0 && band_ok && nrows >= 1) return 2;
-  const int rollov = fd_roll_override();
+  const bool lanes16 = align16 && m % vw == 0;
   const int64_t rowbytes = m * (int64_t)tsize;
-  const int64_t longrow = fd_longrow();
-  const bool roll_shape =
-      rowbytes > longrow ||
-      (rowbytes * 8 >= longrow * 5 && (nrows % 1024) != 0);
-  if (bandov == 0 && rollov == 0 && band_ok &&
-      fd_band_auto(rowbytes, nrows, longrow))
-    return 2;
-  if (V > 1 && (rollov > 0 || (rollov == 0 && roll_shape))) return 1;
-  return 0;
+  // Auto rules (12-shape crossover sweep).  Rolling wins
+  // above longrow (strict: the 4 MiB power-of-two shape prefers
+  // row-parallel) and on "ragged" shapes — rows of at least 5/8 longrow
+  // (2.5 MiB) with a row count that is no multiple of 1024, which the
+  // row-parallel grid maps unevenly across the 8 XCDs.  The band kernel
+  // takes the ragged shapes up to longrow from 4 bands of rows on; fewer
+  // (the overlap path's 1-2-row boundary launches) stay rolling.
+  const bool ragged = rowbytes * 8 >= longrow * 5 && (nrows % 1024) != 0;
+  const bool band_auto = bandov == 0 && rollov == 0 && ragged &&
+                         rowbytes <= longrow && nrows >= 4 * PAM_FD_BAND_RT;
+  const bool roll_auto = rollov == 0 && (rowbytes > longrow || ragged);
+  FdPlan P{FD_ROW, lanes16 ? vw : 1, false, 1, 1};
+  if (lanes16 && ((bandov > 0 && nrows >= 1) || band_auto)) {
+    P.variant = FD_BAND;
+    P.gx = (m / vw + BLK - 1) / BLK;
+    P.gy = (nrows + PAM_FD_BAND_RT - 1) / PAM_FD_BAND_RT;
+  } else if (lanes16 && (rollov > 0 || roll_auto)) {
+    P.variant = FD_ROLL;
+    // 32-B lanes where they divide the row: the rolling form's swept
+    // optimum (the row-parallel kernel's stays 16 B)
+    if (m % 4 == 0) P.V = 4;
+    P.gx = (m / P.V + BLK * PAM_FD_ROLL_CV - 1) / (BLK * PAM_FD_ROLL_CV);
+    // at least 16 rows per chunk, to amortize the 2W+1-row preload
+    const int64_t maxgy = (nrows + 15) / 16;
+    P.gy = rolltgt / P.gx;
+    if (P.gy > maxgy) P.gy = maxgy;
+    if (P.gy < 1) P.gy = 1;
+    if (P.gy > 65535) P.gy = 65535;
+  } else {
+    // one block-row per row; column blocks capped so that a block runs ~4
+    // column iterations at large launches.  262144 blocks in all is the
+    // measured peak between too few blocks and no loop at all (bench shape,
+    // pairs/s by cap: 16384 295.8, 131072 316.6, 262144 332.0, 524288
+    // 319.6, 1048576 = no loop 216.6)
+    const int64_t nb = (m / P.V + BLK - 1) / BLK;
+    P.gy = nrows < gycap ? nrows : gycap;
+    if (P.gy < 1) P.gy = 1;
+    int64_t cap = totcap / P.gy;
+    if (cap < 1) cap = 1;
+    P.gx = nb < cap ? nb : cap;
+    // the unrolled trips need >= 4 iterations per block: with a single
+    // iteration the unrolled kernel is slower than the plain one
+    P.u4 = lanes16 && nb >= 4 * P.gx;
+  }
+  return P;
 }
 
 extern "C" int pam_fd_variant(int dtype, int64_t m, int64_t nrows,
                               int aligned16) {
   if (dtype != PAM_F64 && dtype != PAM_F32) return PAM_EDTYPE;
   if (m <= 0 || nrows < 0) return PAM_EARG;
-  return fd_variant(dtype == PAM_F64 ? 8 : 4, m, nrows, aligned16 != 0);
+  return fd_plan(dtype == PAM_F64 ? 8 : 4, m, nrows, aligned16 != 0).variant;
 }
 
 extern "C" int64_t pam_fd_band_rows(void) { return PAM_FD_BAND_RT; }
+
+// ---- launchers -------------------------------------------------------------
+
+template <typename T>
+struct FdCall {  // the arguments every stencil kernel takes
+  hipStream_t s;
+  Rows<T> R;
+  T* y;
+  int64_t row0, nglob;
+  T c;
+  int edge;
+  int64_t rbegin, rend;
+};
+
+template <typename K, typename T, typename... Extra>
+static int fd_go(K kernel, dim3 grid, const FdCall<T>& a, Extra... extra) {
+  hipLaunchKernelGGL(kernel, grid, dim3(BLK), 0, a.s, a.R, a.y, a.row0,
+                     a.nglob, a.c, a.edge, a.rbegin, a.rend, extra...);
+  return check(hipGetLastError());
+}
+
+template <typename T, int OP>
+static int fd_launch_row(const FdPlan& P, const FdCall<T>& a) {
+  constexpr int VW = VecW<T>::value;
+  const dim3 grid((uint32_t)P.gx, (uint32_t)P.gy);
+  if (P.V == 1) return fd_go(fd_kernel<T, OP, 1, 1>, grid, a);
+  if (P.u4) return fd_go(fd_kernel<T, OP, VW, 4>, grid, a);
+  return fd_go(fd_kernel<T, OP, VW, 1>, grid, a);
+}
+
+template <typename T, int OP>
+static int fd_launch_roll(const FdPlan& P, const FdCall<T>& a) {
+  const dim3 grid((uint32_t)P.gx, (uint32_t)P.gy);
+  if constexpr (VecW<T>::value == 2)
+    if (P.V == 2) return fd_go(fd_roll_kernel<T, OP, 2>, grid, a);
+  return fd_go(fd_roll_kernel<T, OP, 4>, grid, a);
+}
+
+template <typename T, int OP>
+static int fd_launch_band(const FdPlan& P, const FdCall<T>& a) {
+  if (P.gx * P.gy > 0x7fffffffLL) return PAM_EARG;
+  return fd_go(fd_band_kernel<T, OP, VecW<T>::value, PAM_FD_BAND_RT>,
+               dim3((uint32_t)(P.gx * P.gy)), a, (uint32_t)P.gx);
+}
 
 template <typename T, int OP>
 static int fd_launch(void* stream, int edge, const void* x, const void* gf,
@@ -1728,162 +1603,19 @@ static int fd_launch(void* stream, int edge, const void* x, const void* gf,
   if (nloc < 0 || m <= 0 || rbegin < 0 || rend > nloc) return PAM_EARG;
   const int64_t nrows = rend - rbegin;
   if (nloc == 0 || nrows <= 0) return 0;
-  Rows<T> R{(const T*)x, (const T*)gf, (const T*)gb, nloc, m, FDDef<OP>::W};
   const bool align16 = ((uintptr_t)x % 16 == 0) && ((uintptr_t)y % 16 == 0) &&
                        (gf == nullptr || (uintptr_t)gf % 16 == 0) &&
                        (gb == nullptr || (uintptr_t)gb % 16 == 0);
-  int V = fd_vec_width((int)sizeof(T), m, align16);
-  const int variant = fd_variant((int)sizeof(T), m, nrows, align16);
-  hipStream_t s = (hipStream_t)stream;
-  if (variant == 2) {
-    constexpr int BV = VecW<T>::value, RT = PAM_FD_BAND_RT;
-    const int64_t ncb = (m / BV + BLK - 1) / BLK;
-    const int64_t nbands = (nrows + RT - 1) / RT;
-    if (ncb * nbands > 0x7fffffffLL) return PAM_EARG;
-    hipLaunchKernelGGL((fd_band_kernel<T, OP, BV, RT>),
-                       dim3((uint32_t)(ncb * nbands)), dim3(BLK), 0, s, R,
-                       (T*)y, row0, nglob, (T)coeff, edge, rbegin, rend,
-                       (uint32_t)ncb);
-    return check(hipGetLastError());
+  const FdPlan P = fd_plan((int)sizeof(T), m, nrows, align16);
+  const FdCall<T> a{(hipStream_t)stream,
+                    {(const T*)x, (const T*)gf, (const T*)gb, nloc, m,
+                     FDDef<OP>::W},
+                    (T*)y, row0, nglob, (T)coeff, edge, rbegin, rend};
+  switch (P.variant) {
+    case FD_BAND: return fd_launch_band<T, OP>(P, a);
+    case FD_ROLL: return fd_launch_roll<T, OP>(P, a);
+    default: return fd_launch_row<T, OP>(P, a);
   }
-  const int64_t mv = m / V;
-  // Grid shape (PAM_FD_GY / PAM_FD_CAP override for A/Bs): one block-row
-  // per local row (gy = nrows), column blocks sized so each block runs
-  // ~4 vector iterations (total blocks ~= work/(BLK*4)).  Bench A/Bs on
-  // one box, 2-3 reps each (pairs/s at 2048x2048x128 fp64):
-  //   old default gy<=512/cap=4096: 286.7
-  //   gy=nrows cap=16384: 295.8   cap=131072: 316.6
-  //   cap=262144: 332.0 (the peak — frac 0.719)   cap=524288: 319.6
-  //   cap=1048576 (no loop at all): 216.6 (hard regression)
-  static int gycap = [] {
-    const char* e = getenv("PAM_FD_GY");
-    return e ? atoi(e) : 65535;
-  }();
-  static int totcap = [] {
-    const char* e = getenv("PAM_FD_CAP");
-    return e ? atoi(e) : 262144;
-  }();
-  int gy = (int)(nrows < gycap ? nrows : gycap);
-  if (gy < 1) gy = 1;
-  int64_t gx64 = (mv + BLK - 1) / BLK;
-  int64_t cap = totcap / gy;
-  if (cap < 1) cap = 1;
-  if (gx64 > cap) gx64 = cap;
-  dim3 grid((uint32_t)gx64, (uint32_t)gy);
-  // rolling-window path: DEFAULT for long rows (r02).  r01's negative
-  // A/B predates the constexpr-folded window; the r02 PMC runs show the
-  // row-parallel kernel's neighbour-row re-reads really go to HBM once
-  // a row outgrows L2 absorption (FETCH 8.53 GB vs 4.29 algorithmic at
-  // 512x4096x256 => 4.85 TB/s algorithmic), while the rolling kernel
-  // moves exactly 1R+1W (PMC 1.035x) and measures 5.35 TB/s there with
-  // V=4/CV=8/TGT=2048 (the swept optimum; NT stores -15%, roll2's
-  // static rotation spills at CV8V4).  The bench shape (2 MiB rows)
-  // keeps the row-parallel kernel (5.78 vs 5.22).  PAM_FD_ROLL: unset =
-  // auto, -1 = force row-parallel, > 0 = force rolling (the statically-
-  // rotated variant that 2 used to select is gone: DESIGN.md, negative
-  // results).  The r02s10/s11 12-shape crossover
-  // sweep (profiles/) refined the auto rule: the rolling kernel is
-  // flat (~5.0-5.3 TB/s) while row-parallel is peaky (4.8-5.7), and
-  // row-parallel loses not only above 4 MiB rows but ALSO at mid-size
-  // rows whenever the local row count is not a multiple of 1024 (its
-  // gy row-grid then maps raggedly across the 8 XCDs and the L2
-  // neighbour-row grouping degrades: 1536-row shapes lose 4-7% at
-  // 2.5-3 MiB rows).  Rule (fits all 12 measured shapes): roll when
-  // rowbytes > PAM_FD_LONGROW (default 4 MiB, strict — the 4 MiB
-  // power-of-two shape prefers row-parallel), or when rowbytes >=
-  // 5/8 of it (2.5 MiB) and nrows % 1024 != 0.
-  // The rule itself lives in fd_variant.
-  const int rollov = fd_roll_override();
-  const bool roll_auto = rollov == 0 && variant == 1;
-  static int rolltgt = [] {
-    const char* e = getenv("PAM_FD_ROLL_TGT");
-    return e ? atoi(e) : 2048;
-  }();
-  if (variant == 1) {
-    // upgrade to 32-B lanes for the rolling form (its swept optimum;
-    // the row-parallel kernel's optimum stays 16 B)
-    if (roll_auto && fd_vec_override() == 0 && m % 4 == 0 && align16)
-      V = 4;
-    static int cvov = [] {
-      const char* e = getenv("PAM_FD_ROLL_CV");
-      return e ? atoi(e) : 8;
-    }();
-    const int CV = (cvov == 2 || cvov == 4) ? cvov : 8;
-    const int64_t mv2 = m / V;
-    int64_t gx = (mv2 + (int64_t)BLK * CV - 1) / ((int64_t)BLK * CV);
-    int64_t gyr = rolltgt / (gx ? gx : 1);
-    const int64_t minchunk = 16;  // amortize the 2W+1-row preload
-    int64_t maxgy = (nrows + minchunk - 1) / minchunk;
-    if (gyr > maxgy) gyr = maxgy;
-    if (gyr < 1) gyr = 1;
-    if (gyr > 65535) gyr = 65535;
-    dim3 gridr((uint32_t)gx, (uint32_t)gyr);
-    const bool rnt = fd_nt_override() != 0;
-    static int ntlov = [] {
-      const char* e = getenv("PAM_FD_NTL");
-      return e ? atoi(e) : 0;
-    }();
-    const bool rntl = ntlov != 0;
-#define ROLL_LAUNCH(KER, VV, CC)                                              \
-  do {                                                                        \
-    if (rnt)                                                                  \
-      hipLaunchKernelGGL((KER<T, OP, VV, CC, true>), gridr, dim3(BLK), 0, s,  \
-                         R, (T*)y, row0, nglob, (T)coeff, edge, rbegin,       \
-                         rend);                                               \
-    else                                                                      \
-      hipLaunchKernelGGL((KER<T, OP, VV, CC, false>), gridr, dim3(BLK), 0, s, \
-                         R, (T*)y, row0, nglob, (T)coeff, edge, rbegin,       \
-                         rend);                                               \
-  } while (0)
-#define ROLL_LAUNCH1(VV, CC)                                                  \
-  do {                                                                        \
-    if (rntl)                                                                 \
-      hipLaunchKernelGGL((fd_roll_kernel<T, OP, VV, CC, false, true>),        \
-                         gridr, dim3(BLK), 0, s, R, (T*)y, row0, nglob,       \
-                         (T)coeff, edge, rbegin, rend);                       \
-    else                                                                      \
-      ROLL_LAUNCH(fd_roll_kernel, VV, CC);                                    \
-  } while (0)
-    if (V == 4 && CV == 2) ROLL_LAUNCH1(4, 2);
-    else if (V == 4 && CV == 8) ROLL_LAUNCH1(4, 8);
-    else if (V == 4) ROLL_LAUNCH1(4, 4);
-    else if (CV == 2) ROLL_LAUNCH1(2, 2);
-    else if (CV == 8) ROLL_LAUNCH1(2, 8);
-    else ROLL_LAUNCH1(2, 4);
-#undef ROLL_LAUNCH1
-#undef ROLL_LAUNCH
-    return check(hipGetLastError());
-  }
-  const bool nt = fd_nt_override() != 0;
-  if (nt) {
-    if (V == 4)
-      hipLaunchKernelGGL((fd_kernel<T, OP, 4, true>), grid, dim3(BLK), 0, s,
-                         R, (T*)y, row0, nglob, (T)coeff, edge, rbegin, rend);
-    else if (V == 2 && sizeof(T) == 8)
-      hipLaunchKernelGGL((fd_kernel<T, OP, 2, true>), grid, dim3(BLK), 0, s,
-                         R, (T*)y, row0, nglob, (T)coeff, edge, rbegin, rend);
-    else
-      hipLaunchKernelGGL((fd_kernel<T, OP, 1, true>), grid, dim3(BLK), 0, s,
-                         R, (T*)y, row0, nglob, (T)coeff, edge, rbegin, rend);
-  } else if (V == VecW<T>::value && (mv + BLK - 1) / BLK >= 4 * gx64)
-    // >= 4 column iterations per block at 16-B lanes (every large launch:
-    // the grid cap above sets ~4): the 4x-unrolled interior path.  At the
-    // bench shape 5.87 -> 6.10 TB/s, the interior path alone 5.97; with a
-    // single iteration per block the unrolled kernel is slower than the
-    // plain one (4.3 vs 5.9 TB/s at 64 rows), so it is not used there.
-    hipLaunchKernelGGL((fd_kernel<T, OP, VecW<T>::value, false, 4>), grid,
-                       dim3(BLK), 0, s, R, (T*)y, row0, nglob, (T)coeff, edge,
-                       rbegin, rend);
-  else if (V == 4)
-    hipLaunchKernelGGL((fd_kernel<T, OP, 4>), grid, dim3(BLK), 0, s, R, (T*)y,
-                       row0, nglob, (T)coeff, edge, rbegin, rend);
-  else if (V == 2 && sizeof(T) == 8)
-    hipLaunchKernelGGL((fd_kernel<T, OP, 2>), grid, dim3(BLK), 0, s, R, (T*)y,
-                       row0, nglob, (T)coeff, edge, rbegin, rend);
-  else
-    hipLaunchKernelGGL((fd_kernel<T, OP, 1>), grid, dim3(BLK), 0, s, R, (T*)y,
-                       row0, nglob, (T)coeff, edge, rbegin, rend);
-  return check(hipGetLastError());
 }
 
 extern "C" int pam_fd_apply(void* stream, int op, int edge, const void* x,
@@ -1891,26 +1623,13 @@ extern "C" int pam_fd_apply(void* stream, int op, int edge, const void* x,
                             int64_t nloc, int64_t m, int64_t row0,
                             int64_t nglob, int64_t rbegin, int64_t rend,
                             double coeff, int dtype) {
-#define FD_CASE(T)                                                            \
-  switch (op) {                                                               \
-    case 0: return fd_launch<T, 0>(stream, edge, x, gf, gb, y, nloc, m, row0, nglob, rbegin, rend, coeff); \
-    case 1: return fd_launch<T, 1>(stream, edge, x, gf, gb, y, nloc, m, row0, nglob, rbegin, rend, coeff); \
-    case 2: return fd_launch<T, 2>(stream, edge, x, gf, gb, y, nloc, m, row0, nglob, rbegin, rend, coeff); \
-    case 3: return fd_launch<T, 3>(stream, edge, x, gf, gb, y, nloc, m, row0, nglob, rbegin, rend, coeff); \
-    case 4: return fd_launch<T, 4>(stream, edge, x, gf, gb, y, nloc, m, row0, nglob, rbegin, rend, coeff); \
-    case 5: return fd_launch<T, 5>(stream, edge, x, gf, gb, y, nloc, m, row0, nglob, rbegin, rend, coeff); \
-    case 6: return fd_launch<T, 6>(stream, edge, x, gf, gb, y, nloc, m, row0, nglob, rbegin, rend, coeff); \
-    case 7: return fd_launch<T, 7>(stream, edge, x, gf, gb, y, nloc, m, row0, nglob, rbegin, rend, coeff); \
-    case 8: return fd_launch<T, 8>(stream, edge, x, gf, gb, y, nloc, m, row0, nglob, rbegin, rend, coeff); \
-    case 9: return fd_launch<T, 9>(stream, edge, x, gf, gb, y, nloc, m, row0, nglob, rbegin, rend, coeff); \
-    case 10: return fd_launch<T, 10>(stream, edge, x, gf, gb, y, nloc, m, row0, nglob, rbegin, rend, coeff); \
-    case 11: return fd_launch<T, 11>(stream, edge, x, gf, gb, y, nloc, m, row0, nglob, rbegin, rend, coeff); \
-    case 12: return fd_launch<T, 12>(stream, edge, x, gf, gb, y, nloc, m, row0, nglob, rbegin, rend, coeff); \
-    case 13: return fd_launch<T, 13>(stream, edge, x, gf, gb, y, nloc, m, row0, nglob, rbegin, rend, coeff); \
-    default: return PAM_EOP;                                                  \
-  }
-  if (dtype == PAM_F64) { FD_CASE(double) }
-  if (dtype == PAM_F32) { FD_CASE(float) }
-#undef FD_CASE
-  return PAM_EDTYPE;
+  if (dtype != PAM_F64 && dtype != PAM_F32) return PAM_EDTYPE;
+  return fd_dispatch_op(op, [&](auto opc) {
+    constexpr int OP = decltype(opc)::value;
+    return dtype == PAM_F64
+               ? fd_launch<double, OP>(stream, edge, x, gf, gb, y, nloc, m,
+                                       row0, nglob, rbegin, rend, coeff)
+               : fd_launch<float, OP>(stream, edge, x, gf, gb, y, nloc, m,
+                                      row0, nglob, rbegin, rend, coeff);
+  });
 }

@@ -4,23 +4,18 @@ pylops_mpi/utils/deps.py:58-66 (NCCL_PYLOPS_MPI / PYLOPS_MPI_CUDA_AWARE):
   PAM_DISABLE_OVERLAP=1   serialize the halo exchange before the stencil
                           kernel instead of overlapping it with the
                           interior rows (debug aid)
-  PAM_FD_VEC={1,2,4}      force the stencil kernel's per-lane vector width
-                          (default: measured optimum, 16 B/lane)
-  PAM_FD_NT=1             nt cache hint on the stencil's output stores
-                          (measured no-change on the production kernel —
-                          documented negative, csrc/pam.hip)
-  PAM_FD_GY / PAM_FD_CAP  stencil launch-shape A/B knobs (defaults: one
-                          block-row per row, ~4 vector iterations per
-                          block — the measured optimum, csrc/pam.hip)
+  PAM_FD_GY / PAM_FD_CAP  row-parallel stencil launch-shape A/B knobs
+                          (defaults: one block-row per row, ~4 vector
+                          iterations per block — the measured optimum,
+                          csrc/pam.hip fd_plan)
   PAM_FD_ROLL             rolling-window stencil select: unset = AUTO
-                          (rows >= PAM_FD_LONGROW bytes, default 4 MiB,
-                          use the 1-load/pt rolling kernel — the r02
-                          long-row fix, 4.85 -> 5.35 TB/s at the N=8
-                          per-rank shape); -1 = force row-parallel;
-                          > 0 = force rolling (the statically-rotated
-                          variant 2 used to select spilled at CV8xV4 and
-                          was removed, as was the PAM_FD_RSWAP block
-                          mapping, -18% at the bench shape)
+                          (rows > PAM_FD_LONGROW bytes, default 4 MiB, or
+                          >= 5/8 of it with a row count that is no
+                          multiple of 1024, use the 1-load/pt rolling
+                          kernel — the r02 long-row fix, 4.85 -> 5.35 TB/s
+                          at the N=8 per-rank shape); -1 = force
+                          row-parallel; > 0 = force rolling wherever 16-B
+                          lanes exist
   PAM_FD_BAND             row-band stencil select (RT rows of one 16-B
                           column vector per thread, RT+2W loads up front):
                           unset = AUTO, 1 = band wherever eligible (16-B
@@ -34,9 +29,8 @@ pylops_mpi/utils/deps.py:58-66 (NCCL_PYLOPS_MPI / PYLOPS_MPI_CUDA_AWARE):
                           lost to the row-parallel kernel at the bench
                           shape and to the rolling kernel above 4 MiB rows
                           (DESIGN.md)
-  PAM_FD_ROLL_CV / PAM_FD_ROLL_TGT  rolling chains per thread (default
-                          8) and target grid size (default 2048) — the
-                          r02 swept optima
+  PAM_FD_ROLL_TGT         rolling kernel's target grid size (default 2048,
+                          the r02 swept optimum)
   PAM_CGEMM_TILE/_NBUF/_BK  cgemm pipeline A/B knobs (defaults measured
                           best at the cfg5 shapes; 128x64 tile, NBUF=1
                           and BK=8 all measured neutral-to-negative,
@@ -48,6 +42,10 @@ pylops_mpi/utils/deps.py:58-66 (NCCL_PYLOPS_MPI / PYLOPS_MPI_CUDA_AWARE):
                           blocking readback per dot) instead of the
                           single-sync device-scalar iteration (debug aid;
                           both paths are bit-identical)
+
+The stencil knobs that only selected measured-negative code went with that
+code (DESIGN.md "Negative results kept"): lane-width forcing, nt stores and
+loads, and the rolling kernel's chains per thread, now the constant 8.
 
 The RCCL data plane itself has no gate: it IS the backend (there is no
 MPI in this stack to fall back to)."""

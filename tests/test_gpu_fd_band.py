@@ -241,10 +241,11 @@ def test_unrolled_row_kernel_equals_band(monkeypatch):
     """The row-parallel kernel runs its 4x-unrolled interior path once a
     block has >= 4 column iterations, which the launch grid only reaches
     at about 2^28 column vectors per launch: one launch of that size, with
-    a remainder after the unrolled trips, against the band kernel."""
+    a remainder after the unrolled trips, against the band kernel.  One op
+    per (term count, halo width) class: NT = 2, 3, 4 and W = 1, 2."""
     nloc, m = 2048, 2 * (131072 + 300)
     x = randn((nloc, m), torch.float64, 14)
-    for op in (4, 5):
+    for op in (4, 5, 7, 12):
         band_equals_row(monkeypatch, x, None, None, op, False, 0, nloc, 0,
                         nloc)
 
