@@ -16,6 +16,10 @@
  *  - `dtype`: 0 = float64, 1 = float32, 2 = complex128, 3 = complex64
  *    (complex: interleaved re,im pairs of the base type).
  *  - scalar outputs (`out`) are single-element float64 device buffers.
+ *  - n == 0: the element-wise, (de)interleave and reduction entry points
+ *    launch nothing, read no array and accept NULL array pointers (an
+ *    empty block has no storage); the reductions still write their empty
+ *    result to `out`.
  */
 #ifndef PAM_H
 #define PAM_H
@@ -106,7 +110,10 @@ int pam_conj(void* stream, void* y, const void* x, int64_t n, int dtype);
 /* Thresholding for ISTA/FISTA (pylops _softthreshold/_hardthreshold/
  * _halfthreshold formulas, imported by ref optimization/cls_sparsity.py:10;
  * half = the published Xu et al. 2012 L1/2 prox, see pam.hip).
- * kind: 0 = soft, 1 = hard, 2 = half.  In-place safe (y may equal x). */
+ * kind: 0 = soft, 1 = hard, 2 = half.  In-place safe (y may equal x).
+ * NaN: kind 0 returns NaN for a NaN input on real dtypes too, as NumPy's
+ * sign(x) * maximum(|x| - t, 0) does (the complex soft branch and kind 2
+ * propagate it through their products); finite inputs are unaffected. */
 int pam_thresh(void* stream, void* y, const void* x, int64_t n, int kind,
                double thresh, int dtype);
 
@@ -132,7 +139,15 @@ int pam_cdot(void* stream, const void* x, const void* y, int64_t n,
 /* Local part of DistributedArray.norm / _compute_vector_norm
  * (ref :719-838).  op: 0 = sum(|x^p|) (float_power semantics, ref :786),
  * 1 = max(|x|), 2 = min(|x|), 3 = count_nonzero.  Complex dtypes reduce
- * over |z| (|z^p| == |z|^p for real p). */
+ * over |z| (|z^p| == |z|^p for real p).
+ * NaN: ops 1 and 2 return NaN if any element is NaN, as np.max(np.abs(x))
+ * and np.min do (every combine of the tree propagates it); op 0 returns
+ * NaN through the sum and op 3 counts a NaN as nonzero.  This holds for
+ * the LOCAL block: the caller's cross-rank max / min allreduce is RCCL's,
+ * and whether that propagates NaN is RCCL's behaviour, not this
+ * library's.
+ * n == 0: x (and y of pam_dot / pam_cdot) is not read and may be NULL;
+ * out = 0, 0, +inf, 0 for ops 0..3 and 0 for the dot products. */
 int pam_norm_local(void* stream, const void* x, int64_t n, int op, double p,
                    void* ws, void* out, int dtype);
 

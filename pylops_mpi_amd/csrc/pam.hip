@@ -203,8 +203,9 @@ EW_ENTRY(pam_xpby(void* stream, void* y, const void* x, double beta,
 template <typename T, int OP>
 static int ewd_launch(void* stream, void* y, const void* a, const void* ap,
                       double scale, int64_t n) {
-  if (n < 0 || !y || !a || !ap) return PAM_EARG;
-  if (n == 0) return 0;
+  if (n < 0) return PAM_EARG;
+  if (n == 0) return 0;  // an empty block has no storage: y, a may be NULL
+  if (!y || !a || !ap) return PAM_EARG;
   constexpr int V = VecW<T>::value;
   const bool aligned =
       ((uintptr_t)y % 16 == 0) && ((uintptr_t)a % 16 == 0);
@@ -388,8 +389,9 @@ __global__ void __launch_bounds__(BLK) zip_kernel(
 template <typename T>
 static int zip_launch(void* stream, void* dst, const void* src, int64_t n,
                       bool unzip) {
-  if (n < 0 || !dst || !src) return PAM_EARG;
-  if (n == 0) return 0;
+  if (n < 0) return PAM_EARG;
+  if (n == 0) return 0;  // empty arrays have no storage (NULL)
+  if (!dst || !src) return PAM_EARG;
   constexpr int V = VecW<T>::value;
   const bool aligned = ((uintptr_t)dst % 16 == 0) &&
                        ((uintptr_t)src % 16 == 0);
@@ -567,7 +569,8 @@ __global__ void __launch_bounds__(BLK) thresh_kernel(T* __restrict__ y,
       const T v = x[i];
       if constexpr (KIND == 0) {
         const T m = fabs(v) - thresh;
-        y[i] = m > (T)0 ? copysign(m, v) : (T)0;
+        // NaN in, NaN out (sign(x) * max(|x| - t, 0) in NumPy): m is NaN
+        y[i] = m > (T)0 ? copysign(m, v) : (m != m ? m : (T)0);
       } else if constexpr (KIND == 1) {
         y[i] = fabs(v) >= sqrt((T)2 * thresh) ? v : (T)0;
       } else {
@@ -626,10 +629,13 @@ extern "C" int pam_thresh(void* stream, void* y, const void* x, int64_t n,
 // reductions (ref DistributedArray.py:685-717 dot, :719-838 norms)
 // RED codes: 0 dot, 1 powsum |x^p|, 2 max|x|, 3 min|x|, 4 count_nonzero
 // ---------------------------------------------------------------------------
+// max / min propagate NaN, as np.max(np.abs(x)) does (fmax / fmin return
+// the non-NaN operand: a diverged iterate would report a finite inf-norm);
+// on |x| >= +0 without NaN they return what fmax / fmin return.
 template <int RED>
 __device__ __forceinline__ double red_combine(double u, double v) {
-  if constexpr (RED == 2) return fmax(u, v);
-  else if constexpr (RED == 3) return fmin(u, v);
+  if constexpr (RED == 2) return u != u ? u : ((v != v || v > u) ? v : u);
+  else if constexpr (RED == 3) return u != u ? u : ((v != v || v < u) ? v : u);
   else return u + v;
 }
 
@@ -713,14 +719,14 @@ __global__ void __launch_bounds__(BLK) reduce_stage2(
 template <typename T, int RED, bool CPLX = false>
 static int reduce_launch(void* stream, const void* x, const void* y, int64_t n,
                          double p, void* ws, void* out) {
-  if (n < 0 || !x || !ws || !out) return PAM_EARG;
+  if (n < 0 || !ws || !out) return PAM_EARG;
   hipStream_t s = (hipStream_t)stream;
-  if (n == 0) {
+  if (n == 0) {  // x, y are not read: an empty block's pointer is NULL
     double z = (RED == 3) ? INFINITY : 0.0;
     // degenerate case: blocking copy (no stack-lifetime hazard)
     return check(hipMemcpy(out, &z, sizeof(double), hipMemcpyHostToDevice));
   }
-  (void)s;
+  if (!x || (RED == 0 && !y)) return PAM_EARG;
   int64_t nb = (n + BLK - 1) / BLK;
   if (nb > NPARTIAL) nb = NPARTIAL;
   hipLaunchKernelGGL((reduce_stage1<T, RED, CPLX>), dim3(nb), dim3(BLK), 0, s,
@@ -776,12 +782,13 @@ __global__ void __launch_bounds__(BLK) cdot_stage2(
 template <typename T>
 static int cdot_launch(void* stream, const void* x, const void* y, int64_t n,
                        int conjx, void* ws, void* out) {
-  if (n < 0 || !x || !y || !ws || !out) return PAM_EARG;
+  if (n < 0 || !ws || !out) return PAM_EARG;
   hipStream_t s = (hipStream_t)stream;
-  if (n == 0) {
+  if (n == 0) {  // x, y are not read: an empty block's pointer is NULL
     double z[2] = {0.0, 0.0};
     return check(hipMemcpy(out, z, sizeof(z), hipMemcpyHostToDevice));
   }
+  if (!x || !y) return PAM_EARG;
   int64_t nb = (n + BLK - 1) / BLK;
   if (nb > NPARTIAL) nb = NPARTIAL;
   double* pre = (double*)ws;
@@ -810,7 +817,6 @@ extern "C" int pam_cdot(void* stream, const void* x, const void* y, int64_t n,
 
 extern "C" int pam_dot(void* stream, const void* x, const void* y, int64_t n,
                        void* ws, void* out, int dtype) {
-  if (!y) return PAM_EARG;
   if (dtype == PAM_F64)
     return reduce_launch<double, 0>(stream, x, y, n, 0.0, ws, out);
   if (dtype == PAM_F32)
