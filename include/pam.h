@@ -269,7 +269,12 @@ int pam_gemv(void* stream, int trans, const void* A, const void* x, void* y,
 
 /* ------------------------------------------------------------------ *
  * Panel GEMM: C = A @ B (accumulate != 0: C += A @ B) for row-major
- * A [M,K] (lda), B [K,N] (ldb), C [M,N] (ldc).
+ * A [M,K] (lda), B [K,N] (ldb), C [M,N] (ldc).  The leading dimensions
+ * count elements between the starts of consecutive rows: lda >= K,
+ * ldb >= N and ldc >= N are required (PAM_EARG otherwise, nothing is
+ * launched); the ld - row padding is never read and never written.
+ * K == 0 is an empty sum: C is zeroed, or with accumulate left as it is.
+ * PAM_EARG also for M <= 0, N <= 0, K < 0 or a NULL pointer.
  *
  * The local panel product of MPIMatrixMult — block kind
  * (ref basicoperators/MatrixMult.py:369-372 `ncp.matmul(A_local,
@@ -289,7 +294,13 @@ int pam_transpose(void* stream, const void* A, void* At, int64_t nr,
 /* Batched complex GEMM: for b in [0, batch):
  *   C_b (+)= op(A_b) @ B_b  with op = N (opa=0) or conjugate-transpose
  *   (opa=1; then A_b is [K, M]); accumulate != 0 adds into C.
- * A_b = A + b*strideA etc. (strides in ELEMENTS = complex pairs).
+ * A_b = A + b*strideA etc. (strides in ELEMENTS = complex pairs); each
+ * A_b, B_b, C_b is dense (leading dimension = its row length).  The
+ * strides of the inputs may be 0 (one A, or one B, for every batch) or
+ * leave a gap between batches; strideC must be at least M * N, and the
+ * gaps are never read and never written.
+ * K == 0 is an empty sum: every C_b is zeroed, or with accumulate left
+ * as it is.  PAM_EARG for batch, M or N <= 0, K < 0 or a NULL pointer.
  * The Fredholm1 batched integral kernel (ref signalprocessing/
  * Fredholm1.py:123 `ncp.matmul(G, x)` and :149-156 adjoint), and —
  * with batch=1 — the complex MatrixMult panel product
@@ -300,7 +311,8 @@ int pam_cgemm_batched(void* stream, const void* A, const void* B, void* C,
                       int opa, int accumulate, int dtype);
 
 /* Batched REAL GEMM: the single-plane analogue of pam_cgemm_batched
- * (op = N or transpose; accumulate != 0 adds into C).  The Fredholm1
+ * (op = N or transpose; accumulate != 0 adds into C; strides in
+ * elements, K == 0 and the argument errors as there).  The Fredholm1
  * path for float32/float64 kernels (ref Fredholm1.py:123 on a real G)
  * — one z-batched launch instead of a per-slice host loop. */
 int pam_gemm_batched(void* stream, const void* A, const void* B, void* C,

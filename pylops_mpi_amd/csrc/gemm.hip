@@ -251,6 +251,8 @@ static int gemm_launch(void* stream, const void* A, const void* B, void* C,
                        int64_t ldb, int64_t ldc, int accumulate) {
   using CFG = GemmCfg<T>;
   if (M <= 0 || N <= 0 || K < 0 || !A || !B || !C) return PAM_EARG;
+  // a leading dimension shorter than its row would read the wrong rows
+  if (lda < K || ldb < N || ldc < N) return PAM_EARG;
   dim3 grid((uint32_t)((N + CFG::BN - 1) / CFG::BN),
             (uint32_t)((M + CFG::BM - 1) / CFG::BM));
   hipStream_t s = (hipStream_t)stream;
