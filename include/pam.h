@@ -243,6 +243,46 @@ int pam_nsconv(void* stream, int forward, const void* x, void* y,
                const void* hs, int64_t batch, int64_t d, int64_t m,
                int64_t nf, int64_t hsize, double oh, double dh, int dtype);
 
+/* Stationary 1-D convolution along axis d of [batch, d, m] with nh real
+ * taps h, 0 <= offset < nh the tap at lag zero (pylops Convolve1D; with
+ * deriv the implicit pylops PoststackLinearModelling, one pass, no
+ * intermediate in HBM):
+ *   adjoint == 0: y[b,n,j] = sum_k h[k] * v[b, n-k+offset, j]
+ *   adjoint != 0: y[b,n,j] = sum_k h[k] * x[b, n+k-offset, j]
+ * terms whose sample index leaves [0, d) are skipped (zero padding, no
+ * wrap-around).  acc starts at 0, k ascends, every tap is one rounded
+ * multiply and one rounded add in the block's real type, the result is
+ * stored unscaled.
+ * deriv: 0 none (v = x); 1 centered, 2 forward first derivative with
+ * edge = 0, coeff = 1 — pam_fd_serial ops 4/5 and 0/1.  Forward is C(Dx)
+ * (v = Dx), adjoint D^T(C^T x), bit for bit what pam_fd_serial and
+ * pam_conv1d(deriv = 0) give in that order.
+ * x and y must not alias (every output reads nh inputs).  dtype PAM_F64 or
+ * PAM_F32; a complex block with real taps runs as its real view (m -> 2m).
+ * PAM_EARG: batch, d, m or nh <= 0, offset outside [0, nh), a NULL
+ * pointer; PAM_EOP: deriv outside 0..2; PAM_EDTYPE otherwise; all checked
+ * before anything is launched.
+ *
+ * pam_conv1d_variant: the kernel pam_conv1d runs for that block (host-side
+ * query): 0 plain (one thread per output), 1 trace (a run of flattened
+ * (n, j) outputs and its halo staged in LDS; m small), 2 column (rows x
+ * columns tile in LDS, a register window along d; m large).
+ * PAM_CONV_VARIANT=0|1|2, re-read per call, forces a variant where it is
+ * valid; a tiled variant whose halo ((nh + 1) * m samples for 1, nh + 1
+ * rows for 2) does not fit the LDS budget falls back to 0, and the query
+ * says so.
+ * pam_conv1d_tile_d / _tile_m: what one workgroup owns — variant 2:
+ * tile_d rows of tile_m columns; variant 1: tile_d consecutive flattened
+ * outputs of one batch (tile_d rows when m == 1; tile_m is 1, a run is
+ * not aligned to columns); 0 for variant 0 and where variant 2 does not
+ * fit. */
+int pam_conv1d(void* stream, int adjoint, const void* x, void* y,
+               const void* h, int64_t batch, int64_t d, int64_t m,
+               int64_t nh, int64_t offset, int deriv, int dtype);
+int pam_conv1d_variant(int dtype, int64_t d, int64_t m, int64_t nh);
+int64_t pam_conv1d_tile_d(int variant, int dtype, int64_t nh);
+int64_t pam_conv1d_tile_m(int variant, int dtype);
+
 /* Serial (single-rank) stencil along an arbitrary axis: the block is
  * viewed as [batch, d, m] with the derivative along d.  The local
  * operators inside MPIBlockDiag for Gradient/Laplacian axes >= 1

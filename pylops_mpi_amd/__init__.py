@@ -21,6 +21,10 @@ from .nonstatconv import (MPINonStationaryConvolve1D,  # noqa: F401
                           NonStationaryConvolve1DLocal, halo_block_split)
 from .fdlocal import (FirstDerivativeLocal,  # noqa: F401
                       SecondDerivativeLocal)
+from .convolve import (Convolve1DLocal,  # noqa: F401
+                       PoststackLinearModellingLocal)
+from . import wavelets  # noqa: F401
+from .wavelets import ricker  # noqa: F401
 from .gradient import MPIGradient, MPILaplacian  # noqa: F401
 from .mdc import MPIMDC  # noqa: F401
 from .fftlocal import FFTLocal, IdentityLocal  # noqa: F401

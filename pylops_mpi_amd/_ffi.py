@@ -65,6 +65,10 @@ _SIGS = {
     "pam_transpose": ([P, P, P, L, L, I], I),
     "pam_fd_halo_width": ([I], L),
     "pam_nsconv": ([P, I, P, P, P, L, L, L, L, L, D, D, I], I),
+    "pam_conv1d": ([P, I, P, P, P, L, L, L, L, L, I, I], I),
+    "pam_conv1d_variant": ([I, L, L, L], I),
+    "pam_conv1d_tile_d": ([I, I, L], L),
+    "pam_conv1d_tile_m": ([I, I], L),
     "pam_fd_serial": ([P, I, I, P, P, L, L, L, D, I], I),
     "pam_fd_apply": ([P, I, I, P, P, P, P, L, L, L, L, L, L, D, I], I),
     "pam_fd_variant": ([I, L, L, I], I),

@@ -485,3 +485,62 @@ def nsconv(y, x, hs, forward: bool, oh: float, dh: float):
     _run("pam_nsconv", 1 if forward else 0, x.contiguous(), y,
          hs.contiguous(), batch, d, m, nf, hsize, float(oh), float(dh),
          _code(y.dtype))
+
+
+CONV_PLAIN, CONV_TRACE, CONV_COLUMN = 0, 1, 2  # pam_conv1d_variant codes
+
+
+def conv1d(y, x, h, adjoint: bool, offset: int, deriv: int = 0):
+    """Stationary convolution with the ``nh`` real taps ``h`` along dim 1
+    of the [batch, d, m] block ``x``, ``offset`` the tap at lag zero:
+    y[b,n,j] = sum_k h[k] * x[b, n-k+offset, j] (forward) or
+    sum_k h[k] * x[b, n+k-offset, j] (adjoint), zero-padded at the ends.
+    ``deriv`` fuses a first derivative along the same dim (1 centered,
+    2 forward; edge False, sampling 1): forward C(Dx), adjoint D^T(C^T x),
+    one launch.  Complex blocks run as their real view with doubled m;
+    the taps stay real.  ``x`` and ``y`` must not share memory."""
+    name = "pam_conv1d"
+    rdt = _REAL_OF.get(y.dtype, y.dtype)
+    if h.is_complex():
+        raise TypeError(f"pam: {name}: complex taps are not supported "
+                        f"(got {h.dtype})")
+    _typed(name, y.dtype, x)
+    _typed(name, rdt, h)
+    k, dt = _real_code(y)
+    batch, d, m = x.shape
+    _shaped(name, (batch, d, m), y)
+    if h.ndim != 1 or h.numel() < 1:
+        raise ValueError(f"pam: {name}: taps must be 1-D and non-empty, "
+                         f"got shape {tuple(h.shape)}")
+    nh = h.numel()
+    if not 0 <= int(offset) < nh:
+        raise ValueError(f"pam: {name}: offset {offset} outside [0, {nh})")
+    if int(deriv) not in (0, 1, 2):
+        raise ValueError(f"pam: {name}: deriv {deriv} outside 0..2")
+    _dst(name, y)
+    _run(name, 1 if adjoint else 0, x.contiguous(), y, h.contiguous(),
+         batch, d, k * m, nh, int(offset), int(deriv), dt)
+
+
+def conv1d_variant(x, nh: int) -> int:
+    """The kernel conv1d runs on the [batch, d, m] block ``x`` with ``nh``
+    taps and the environment as it is now: CONV_PLAIN, CONV_TRACE or
+    CONV_COLUMN.  Host-side query; nothing is enqueued."""
+    k, dt = _real_code(x)
+    _, d, m = x.shape
+    v = int(_ffi.lib().pam_conv1d_variant(dt, d, k * m, int(nh)))
+    if v < 0:
+        _ffi.checked(v, "pam_conv1d_variant")
+    return v
+
+
+def conv1d_tile(variant: int, dtype, nh: int):
+    """(tile_d, tile_m) one workgroup of ``variant`` owns for blocks of
+    torch ``dtype`` (complex: of its real view) and ``nh`` taps; (0, 0)
+    for CONV_PLAIN.  See pam_conv1d_tile_d in include/pam.h."""
+    dt = _AS_REAL[dtype][1] if dtype in _AS_REAL else _code(dtype)
+    td = int(_ffi.lib().pam_conv1d_tile_d(int(variant), dt, int(nh)))
+    tm = int(_ffi.lib().pam_conv1d_tile_m(int(variant), dt))
+    if td < 0 or tm < 0:
+        _ffi.checked(min(td, tm), "pam_conv1d_tile")
+    return td, tm
