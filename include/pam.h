@@ -283,6 +283,87 @@ int pam_conv1d_variant(int dtype, int64_t d, int64_t m, int64_t nh);
 int64_t pam_conv1d_tile_d(int variant, int dtype, int64_t nh);
 int64_t pam_conv1d_tile_m(int variant, int dtype);
 
+/* Kinematic Kirchhoff demigration / migration: the traveltime spread and
+ * gather of pylops Kirchhoff with dynamic = False and wavfilter = False
+ * (what pylops LSM(..., mode = "analytic") builds; the per-rank operator of
+ * the reference's tutorials/lsm.py).  pylops' Kirchhoff is
+ *   Convolve1D((ns * nr, nt), wav, offset = wavcenter, axis = -1) o spread;
+ * the wavelet stage is pam_conv1d, this entry point is the spread and its
+ * adjoint.
+ *
+ * Model m: ni image points, (nx, nz) or (ny, nx, nz) flattened in C order.
+ * Data d: [ns, nr, nt], trace k = is * nr + ir, time axis starting at 0.
+ * Tables qs [ns, ni] and qr [nr, ni]: source-to-point and point-to-receiver
+ * traveltimes in units of SAMPLES, trace-major (lanes run over i and the
+ * loads coalesce): qs[is, i] = trav_srcs[i, is] / dt for pylops' tables
+ * trav_srcs (ni, ns) in seconds, qr likewise.  Adding two tables that were
+ * divided by dt once, instead of dividing the sum per pair as pylops'
+ * (ts + tr) / dt does, is a deliberate deviation by one rounding of q; it
+ * is harmless because linear interpolation is continuous across a sample
+ * boundary: a q that lands an ulp on the other side of an integer moves a
+ * weight of about one ulp between two neighbouring samples.
+ *
+ * Per pair (k, i), everything in the block's type T:
+ *   q = qs[is, i] + qr[ir, i],  it = floor(q),  w = q - it
+ * the pair contributes iff 0 <= it < nt - 1; a NaN, infinite or negative q
+ * fails that test, is skipped and indexes nothing.
+ *   adjoint == 0 (spread, demigration):
+ *     d[k, it] += m[i] * (1 - w);  d[k, it + 1] += m[i] * w
+ *     every sample that receives nothing is written as 0: d needs no
+ *     zeroing by the caller.
+ *   adjoint != 0 (gather, migration):
+ *     mig[i] = sum_k ((1 - w) * d[k, it]) + (w * d[k, it + 1]), written
+ *     to m.
+ *
+ * Reproducibility.  The adjoint is pinned: acc = 0, traces ascending,
+ * term = ((1 - w) * d0) + (w * d1) with each operation rounded once,
+ * acc += term; where the launch splits the traces, every run of
+ * pam_kirch_chunk consecutive traces is summed so from 0 and the partial
+ * sums are added in ascending order — a NumPy loop given that chunk
+ * reproduces every bit.  The forward is NOT: a workgroup sums a trace
+ * window in LDS (in float64 for either T) with float adds whose order
+ * depends on the schedule, so a sample is the sum of its n products
+ * m[i] * (1 - w) or m[i] * w, each rounded in T, in SOME order, rounded to
+ * T when written: within (n + 2) eps_T sum |m[i]| weight of the exact
+ * value.  It is the first entry point of this library that is not
+ * reproducible bit for bit; two runs of one launch were seen to differ in
+ * the last bits on MI355X.  No float atomic reaches global memory and no
+ * two workgroups add to one destination.
+ *
+ * ws: device scratch of pam_kirch_ws_elems elements of T (0: may be NULL).
+ * m and d must not share memory.  dtype PAM_F64 or PAM_F32.
+ * PAM_EARG: ns, nr or ni <= 0, nt < 2, a NULL m / d / qs / qr, ws NULL
+ * where elements are needed, m and d overlapping; PAM_EDTYPE otherwise;
+ * all checked before anything is launched.
+ *
+ * Host-side queries (no GPU work; each honours the environment exactly as
+ * the launch does, re-read per call):
+ * pam_kirch_points: image points one workgroup of the adjoint owns.
+ * pam_kirch_chunk: traces per partial sum of the adjoint for that block —
+ *   a fixed count where the traces are split over workgroups (few image
+ *   points), ns * nr where they are not.  PAM_KIRCH_SPLIT=0|1 forces
+ *   either.
+ * pam_kirch_variant: the adjoint's body, 0 samples gathered from global
+ *   memory, 1 each trace staged in LDS first (0 where a trace does not fit
+ *   the LDS budget).  PAM_KIRCH_STAGE=0|1 forces either.
+ * pam_kirch_window: samples W of the time window one workgroup of the
+ *   forward owns: nt where the traces alone fill the chip, shorter with
+ *   few traces, at most the LDS budget (8192 samples: the window is kept
+ *   in float64).  PAM_KIRCH_WINDOW=W forces it (1 <= W <= budget; nt if
+ *   smaller). */
+int pam_kirch(void* stream, int adjoint, void* m, void* d, const void* qs,
+              const void* qr, void* ws, int64_t ns, int64_t nr, int64_t ni,
+              int64_t nt, int dtype);
+int64_t pam_kirch_ws_elems(int adjoint, int64_t ns, int64_t nr, int64_t ni,
+                           int64_t nt, int dtype);
+int64_t pam_kirch_points(void);
+int64_t pam_kirch_chunk(int64_t ns, int64_t nr, int64_t ni, int64_t nt,
+                        int dtype);
+int pam_kirch_variant(int64_t ns, int64_t nr, int64_t ni, int64_t nt,
+                      int dtype);
+int64_t pam_kirch_window(int64_t ns, int64_t nr, int64_t ni, int64_t nt,
+                         int dtype);
+
 /* Serial (single-rank) stencil along an arbitrary axis: the block is
  * viewed as [batch, d, m] with the derivative along d.  The local
  * operators inside MPIBlockDiag for Gradient/Laplacian axes >= 1

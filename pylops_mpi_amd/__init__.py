@@ -23,6 +23,8 @@ from .fdlocal import (FirstDerivativeLocal,  # noqa: F401
                       SecondDerivativeLocal)
 from .convolve import (Convolve1DLocal,  # noqa: F401
                        PoststackLinearModellingLocal)
+from .kirchhoff import (KirchhoffLocal, LSMLocal,  # noqa: F401
+                        traveltime_table)
 from . import wavelets  # noqa: F401
 from .wavelets import ricker  # noqa: F401
 from .gradient import MPIGradient, MPILaplacian  # noqa: F401

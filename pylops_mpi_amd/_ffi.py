@@ -69,6 +69,12 @@ _SIGS = {
     "pam_conv1d_variant": ([I, L, L, L], I),
     "pam_conv1d_tile_d": ([I, I, L], L),
     "pam_conv1d_tile_m": ([I, I], L),
+    "pam_kirch": ([P, I, P, P, P, P, P, L, L, L, L, I], I),
+    "pam_kirch_ws_elems": ([I, L, L, L, L, I], L),
+    "pam_kirch_points": ([], L),
+    "pam_kirch_chunk": ([L, L, L, L, I], L),
+    "pam_kirch_variant": ([L, L, L, L, I], I),
+    "pam_kirch_window": ([L, L, L, L, I], L),
     "pam_fd_serial": ([P, I, I, P, P, L, L, L, D, I], I),
     "pam_fd_apply": ([P, I, I, P, P, P, P, L, L, L, L, L, L, D, I], I),
     "pam_fd_variant": ([I, L, L, I], I),

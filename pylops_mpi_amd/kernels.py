@@ -544,3 +544,84 @@ def conv1d_tile(variant: int, dtype, nh: int):
     if td < 0 or tm < 0:
         _ffi.checked(min(td, tm), "pam_conv1d_tile")
     return td, tm
+
+
+# ------------------------------------------------------------- Kirchhoff
+KIRCH_GATHER, KIRCH_STAGED = 0, 1   # pam_kirch_variant codes
+_kirch_scratch = {}     # per (device, dtype), sized for the largest seen
+
+
+def _kirch_dims(name, d, m, qs, qr):
+    """Dtype and shape checks of a pam_kirch block -> (ns, nr, ni, nt)."""
+    if d.dtype not in (_F64, torch.float32):
+        raise TypeError(f"pam: {name}: expected float64 or float32, got "
+                        f"{d.dtype}")
+    _typed(name, d.dtype, m, qs, qr)
+    ns, nr, nt = d.shape
+    (ni,) = m.shape
+    _shaped(name, (ns, ni), qs)
+    _shaped(name, (nr, ni), qr)
+    if min(ns, nr, ni) < 1 or nt < 2:
+        raise ValueError(f"pam: {name}: needs ns, nr, ni >= 1 and nt >= 2, "
+                         f"got data {tuple(d.shape)}, model {tuple(m.shape)}")
+    return ns, nr, ni, nt
+
+
+def kirchhoff(d, m, qs, qr, adjoint: bool):
+    """Kinematic Kirchhoff spread (``adjoint`` false: d <- m, every sample
+    of d written) or gather (m <- d) between the model ``m`` (ni,) and the
+    data ``d`` (ns, nr, nt), with the traveltime tables in samples
+    ``qs`` (ns, ni) and ``qr`` (nr, ni).  See pam_kirch in include/pam.h.
+    ``m`` and ``d`` must not share memory."""
+    name = "pam_kirch"
+    ns, nr, ni, nt = _kirch_dims(name, d, m, qs, qr)
+    if adjoint:
+        _dst(name, m)
+        d = d.contiguous()
+    else:
+        _dst(name, d)
+        m = m.contiguous()
+    qs, qr = qs.contiguous(), qr.contiguous()
+    idx = require_device(d, m, qs, qr)
+    dt = _code(d.dtype)
+    need = int(_ffi.lib().pam_kirch_ws_elems(1 if adjoint else 0, ns, nr, ni,
+                                             nt, dt))
+    ws = None
+    if need > 0:
+        ws = _kirch_scratch.get((idx, d.dtype))
+        if ws is None or ws.numel() < need:
+            ws = _kirch_scratch[(idx, d.dtype)] = torch.empty(
+                need, dtype=d.dtype, device=d.device)
+    _launch(idx, name, (1 if adjoint else 0, m.data_ptr(), d.data_ptr(),
+                        qs.data_ptr(), qr.data_ptr(),
+                        None if ws is None else ws.data_ptr(), ns, nr, ni,
+                        nt, dt))
+
+
+def _kirch_query(fn, d, m, qs, qr):
+    name = "pam_kirch"
+    ns, nr, ni, nt = _kirch_dims(name, d, m, qs, qr)
+    v = int(getattr(_ffi.lib(), fn)(ns, nr, ni, nt, _code(d.dtype)))
+    if v < 0:
+        _ffi.checked(v, fn)
+    return v
+
+
+def kirchhoff_points() -> int:  # image points per workgroup of the gather
+    return int(_ffi.lib().pam_kirch_points())
+
+
+def kirchhoff_chunk(d, m, qs, qr) -> int:
+    """Traces per partial sum of the gather on that block (ns * nr: the
+    traces are not split), the environment as it is now.  Host-side."""
+    return _kirch_query("pam_kirch_chunk", d, m, qs, qr)
+
+
+def kirchhoff_variant(d, m, qs, qr) -> int:
+    """The gather's body on that block: KIRCH_GATHER or KIRCH_STAGED."""
+    return _kirch_query("pam_kirch_variant", d, m, qs, qr)
+
+
+def kirchhoff_window(d, m, qs, qr) -> int:
+    """Samples of the time window one workgroup of the spread owns."""
+    return _kirch_query("pam_kirch_window", d, m, qs, qr)
