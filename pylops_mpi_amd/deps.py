@@ -31,10 +31,11 @@ pylops_mpi/utils/deps.py:58-66 (NCCL_PYLOPS_MPI / PYLOPS_MPI_CUDA_AWARE):
                           (DESIGN.md)
   PAM_FD_ROLL_TGT         rolling kernel's target grid size (default 2048,
                           the r02 swept optimum)
-  PAM_CGEMM_TILE/_NBUF/_BK  cgemm pipeline A/B knobs (defaults measured
-                          best at the cfg5 shapes; 128x64 tile, NBUF=1
-                          and BK=8 all measured neutral-to-negative,
-                          csrc/gemm.hip)
+  PAM_CGEMM_BK            complex batched GEMM K-panel depth without
+                          accumulate: unset = AUTO (8 for K <= 64, else 16:
+                          each won on its side at the cfg5 shapes,
+                          csrc/gemm.hip cgemm_bk), 8 / 16 = force.  Read
+                          once per process
   PAM_EW_CAP              1-D elementwise grid cap (default: none — one
                           block per 256 vector items; the old 4096-block
                           grid-stride loop cost 28% of axpy bandwidth)
@@ -43,9 +44,10 @@ pylops_mpi/utils/deps.py:58-66 (NCCL_PYLOPS_MPI / PYLOPS_MPI_CUDA_AWARE):
                           single-sync device-scalar iteration (debug aid;
                           both paths are bit-identical)
 
-The stencil knobs that only selected measured-negative code went with that
-code (DESIGN.md "Negative results kept"): lane-width forcing, nt stores and
-loads, and the rolling kernel's chains per thread, now the constant 8.
+The knobs that only selected measured-negative code went with that code
+(DESIGN.md "Negative results kept"): the stencils' lane-width forcing, nt
+stores and loads, and the rolling kernel's chains per thread, now the
+constant 8; the complex GEMM's 128x64 tile and single-buffered panels.
 
 The RCCL data plane itself has no gate: it IS the backend (there is no
 MPI in this stack to fall back to)."""

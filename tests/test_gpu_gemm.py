@@ -23,14 +23,13 @@ dtype.
 
 Variants reached (template arguments), all for T = double and float:
   gemm_kernel<T, ACC, GUARD>: all four, dense and with lda/ldb/ldc padded
-  gemm_batched_kernel<T, CT, ACC>: all four
-  cgemm_batched_kernel<T, CT, ACC, BK>: <CT, false, 8> for K <= 64,
-    <CT, false, 16> above, <CT, true, 16>; in child processes <CT, false,
-    16, 128, 64> (PAM_CGEMM_TILE=2), <CT, false, 16, 64, 64, 1>
-    (PAM_CGEMM_NBUF=1), BK 8 above K = 64 and BK 16 below
-    (PAM_CGEMM_BK=8 / 16)
+  gemm_batched_kernel<T, NPL, CT, ACC, BK>, NPL values per element:
+    real <T, 1, CT, ACC, 16>: all four
+    complex <T, 2, CT, false, 8> for K <= 64, <T, 2, CT, false, 16> above,
+    <T, 2, CT, true, 16>; in child processes BK 8 above K = 64 and BK 16
+    below (PAM_CGEMM_BK=8 / 16)
   gemm256_f32_kernel<ACC>: both, 1, 2, 3 and 16 panels
-  transpose_kernel<T>, ctranspose_kernel<T, CONJ>: all
+  transpose_kernel<T, NV, CONJ>: <T, 1, false>, <T, 2, false>, <T, 2, true>
 
 Worst err / bound seen on an MI355X, per entry point (RATIO collects them,
 WORST the case; the environment-selected variants stay below the same
@@ -292,12 +291,11 @@ print("\\n".join(bad[:25]))
 print("worst err / bound:", t.RATIO)
 sys.exit(1 if bad else 0)
 """
-VARIANTS = [("PAM_CGEMM_TILE", "2"), ("PAM_CGEMM_NBUF", "1"),
-            ("PAM_CGEMM_BK", "8"), ("PAM_CGEMM_BK", "16")]
+VARIANTS = [("PAM_CGEMM_BK", "8"), ("PAM_CGEMM_BK", "16")]
 
 
 def test_cgemm_env_variants():
-    """PAM_CGEMM_TILE / NBUF / BK are read once per process, so each
+    """PAM_CGEMM_BK is read once per process, so each
     setting runs in a fresh child process, one after another; the first
     child that fails, dies or runs out of time ends the test."""
     tests = os.path.dirname(os.path.abspath(__file__))
