@@ -17,9 +17,10 @@
  *    (complex: interleaved re,im pairs of the base type).
  *  - scalar outputs (`out`) are single-element float64 device buffers.
  *  - n == 0: the element-wise, (de)interleave and reduction entry points
- *    launch nothing, read no array and accept NULL array pointers (an
- *    empty block has no storage); the reductions still write their empty
- *    result to `out`.
+ *    read no array and accept NULL array pointers (an empty block has no
+ *    storage).  The element-wise and (de)interleave ones launch nothing;
+ *    the reductions still write their empty result to `out`, from a
+ *    kernel on `stream`: in stream order, with no host-blocking call.
  */
 #ifndef PAM_H
 #define PAM_H

@@ -30,16 +30,10 @@
 // leaves acc unchanged (at most the sign of a zero result differs) for
 // finite taps.  The taps are wave-uniform and come in as scalar loads.
 
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-#include <stdlib.h>
-
-#include "../../include/pam.h"
 #include "fd_defs.h"
 
 #pragma clang fp contract(off)
 
-#define CBLK 256
 #define CONV_R 8          // rows per thread, column kernel
 #define CONV_TM 64        // columns per workgroup, column kernel
 #define CONV_TD_MAX 128   // rows per workgroup, column kernel (at most)
@@ -102,7 +96,7 @@ __device__ __forceinline__ T conv_plain_at(const T* __restrict__ xb,
 }
 
 template <typename T, bool ADJ, int DERIV>
-__global__ void __launch_bounds__(CBLK) conv_plain_kernel(
+__global__ void __launch_bounds__(BLK) conv_plain_kernel(
     const T* __restrict__ x, T* __restrict__ y, const T* __restrict__ h,
     int64_t batch, int64_t d, int64_t m, int64_t nh, int64_t off) {
   const int64_t total = batch * d * m;
@@ -136,7 +130,7 @@ __global__ void __launch_bounds__(CBLK) conv_plain_kernel(
 // outputs (trace) per workgroup.  LDS word 0 is sample row
 // first_output_row - E - HL, HL the taps' reach below an output.
 template <typename T, int R, int TM, bool ADJ, int DERIV>
-__global__ void __launch_bounds__(CBLK) conv_tiled_kernel(
+__global__ void __launch_bounds__(BLK) conv_tiled_kernel(
     const T* __restrict__ x, T* __restrict__ y, const T* __restrict__ h,
     int d, int m, int nh, int off, int td, int ntile_d, int ntile_m) {
   extern __shared__ __align__(16) unsigned char conv_smem[];
@@ -168,7 +162,7 @@ __global__ void __launch_bounds__(CBLK) conv_tiled_kernel(
     // whole row groups: the window of a short last group reads them
     const int nrows = (nout + R - 1) / R * R + 2 * E + nh - 1;
     const int g0 = o0 - E - HL;
-    for (int i = tid; i < nrows * TM; i += CBLK) {
+    for (int i = tid; i < nrows * TM; i += BLK) {
       const int lr = i / TM, lc = i % TM;
       const int g = g0 + lr, c = c0 + lc;
       T v = (T)0;
@@ -184,7 +178,7 @@ __global__ void __launch_bounds__(CBLK) conv_tiled_kernel(
   } else {
     const int nst = nout + (2 * E + nh - 1) * m;
     const int f0 = o0 - (E + HL) * m;
-    for (int i = tid; i < nst; i += CBLK) {
+    for (int i = tid; i < nst; i += BLK) {
       const int f = f0 + i;
       T v = (T)0;
       if (f >= 0 && f < dm) {
@@ -200,7 +194,7 @@ __global__ void __launch_bounds__(CBLK) conv_tiled_kernel(
 
   // ---- items: (row group, column) or one flat output ----
   const int nitems = COL ? ((nout + R - 1) / R) * TM : nout;
-  for (int it = tid; it < nitems; it += CBLK) {
+  for (int it = tid; it < nitems; it += BLK) {
     int ib, fo;        // LDS word of window row 0 at tap row 0; output flat
     int rows = R;      // output rows of this item inside the block
     if constexpr (COL) {
@@ -277,11 +271,6 @@ struct ConvPlan {
   size_t lds;           // dynamic LDS bytes
 };
 
-static int64_t conv_env_variant() {  // read on EVERY call
-  const char* e = getenv("PAM_CONV_VARIANT");
-  return (e && *e) ? atoll(e) : -1;
-}
-
 // rows per workgroup of the column kernel for nh taps: what the LDS budget
 // leaves after the nh - 1 halo rows and the derivative's 2, a multiple of
 // CONV_R, at most CONV_TD_MAX; 0 = does not fit
@@ -310,7 +299,7 @@ static ConvPlan conv_plan(int dtype, int64_t batch, int64_t d, int64_t m,
   const int64_t td2 = conv_col_td(tsize, nh);
   const bool ok1 = idx32 && conv_trace_fits(tsize, m, nh);
   const bool ok2 = idx32 && td2 > 0;
-  const int64_t forced = conv_env_variant();
+  const int64_t forced = env_int("PAM_CONV_VARIANT", -1);  // on EVERY call
   int want;
   if (forced >= 0 && forced <= 2) {
     want = (int)forced;
@@ -377,20 +366,20 @@ static int conv_launch(hipStream_t s, const ConvPlan& P, const void* x,
   const T* hp = (const T*)h;
   T* yp = (T*)y;
   if (P.variant == 0) {
-    int64_t g = (batch * d * m + CBLK - 1) / CBLK;
+    int64_t g = (batch * d * m + BLK - 1) / BLK;
     if (g > 0x7FFFFFFF) g = 0x7FFFFFFF;
     hipLaunchKernelGGL((conv_plain_kernel<T, ADJ, DERIV>), dim3((unsigned)g),
-                       dim3(CBLK), 0, s, xp, yp, hp, batch, d, m, nh, off);
+                       dim3(BLK), 0, s, xp, yp, hp, batch, d, m, nh, off);
   } else {
     const dim3 grid((unsigned)(batch * P.ntd * P.ntm));
     if (P.variant == 1)
       hipLaunchKernelGGL((conv_tiled_kernel<T, 1, 0, ADJ, DERIV>), grid,
-                         dim3(CBLK), P.lds, s, xp, yp, hp, (int)d, (int)m,
+                         dim3(BLK), P.lds, s, xp, yp, hp, (int)d, (int)m,
                          (int)nh, (int)off, (int)P.td, (int)P.ntd,
                          (int)P.ntm);
     else
       hipLaunchKernelGGL((conv_tiled_kernel<T, CONV_R, CONV_TM, ADJ, DERIV>),
-                         grid, dim3(CBLK), P.lds, s, xp, yp, hp, (int)d,
+                         grid, dim3(BLK), P.lds, s, xp, yp, hp, (int)d,
                          (int)m, (int)nh, (int)off, (int)P.td, (int)P.ntd,
                          (int)P.ntm);
   }

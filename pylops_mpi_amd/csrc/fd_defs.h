@@ -4,11 +4,7 @@
 #ifndef PAM_FD_DEFS_H
 #define PAM_FD_DEFS_H
 
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-#include <utility>
-
-#include "../../include/pam.h"
+#include "launch.h"
 
 template <typename T> struct VecW;                // 16-B vector width per T
 template <> struct VecW<double> { static constexpr int value = 2; };
@@ -69,18 +65,6 @@ __device__ __forceinline__ void storev(T* __restrict__ p, const T* v) {
     }
     *reinterpret_cast<VT*>(p) = t;
   }
-}
-
-// f(std::integral_constant<int, 0>{}) ... f(std::integral_constant<int,
-// N-1>{}), in order: a loop whose index is a compile-time constant inside f.
-template <typename F, int... Is>
-__host__ __device__ __forceinline__ void fd_unroll_seq(
-    F&& f, std::integer_sequence<int, Is...>) {
-  (f(std::integral_constant<int, Is>{}), ...);
-}
-template <int N, typename F>
-__host__ __device__ __forceinline__ void fd_unroll(F&& f) {
-  fd_unroll_seq(f, std::make_integer_sequence<int, N>{});
 }
 
 struct Term {
@@ -187,11 +171,7 @@ template <> struct FDDef<13> {
 constexpr int FD_NOPS = 14;
 template <typename F>
 static inline int fd_dispatch_op(int op, F&& f) {
-  int rc = PAM_EOP;
-  fd_unroll<FD_NOPS>([&](auto opc) {
-    if (op == decltype(opc)::value) rc = f(opc);
-  });
-  return rc;
+  return with_int<0, FD_NOPS - 1>(op, PAM_EOP, f);
 }
 
 

@@ -3,15 +3,8 @@
 // reproducibly segfaults clang-22/ROCm 7.2's gfx950 backend (instantiation
 // interaction; the same code compiles alone), so they live here.
 
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-
-#include "../../include/pam.h"
 #include "fd_defs.h"
 
-#define BLK 256
-
-static inline int check_s(hipError_t e) { return (int)e; }
 
 static inline int64_t grid_1d_s(int64_t work) {
   int64_t g = (work + BLK - 1) / BLK;
@@ -103,7 +96,7 @@ static int fd_serial_launch(void* stream, int edge, const void* x, void* y,
   hipLaunchKernelGGL((fd_serial_kernel<T, OP>),
                      dim3(grid_1d_s(batch * d * m)), dim3(BLK), 0, s,
                      (const T*)x, (T*)y, batch, d, m, (T)coeff, edge);
-  return check_s(hipGetLastError());
+  return check(hipGetLastError());
 }
 
 extern "C" int pam_fd_serial(void* stream, int op, int edge, const void* x,
@@ -191,7 +184,7 @@ extern "C" int pam_nsconv(void* stream, int forward, const void* x, void* y,
                          dim3(grid_1d_s(batch * d * m)), dim3(BLK), 0, s,     \
                          (const T*)x, (T*)y, (const T*)hs, batch, d, m, nf,   \
                          hsize, oh, dh);                                      \
-    return check_s(hipGetLastError());                                        \
+    return check(hipGetLastError());                                          \
   } while (0)
   if (dtype == PAM_F64) NSC_CASE(double);
   if (dtype == PAM_F32) NSC_CASE(float);

@@ -20,30 +20,12 @@
 // K-panel gets from global memory into LDS) only: the K-panel pipeline,
 // the fragment loop and the C/D walk below are shared.
 
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-#include <stdlib.h>
-
-#include <type_traits>
-
-#include "../../include/pam.h"
-
-#define GBLK 256
+#include "launch.h"
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef double f64x4 __attribute__((ext_vector_type(4)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef double f64x2 __attribute__((ext_vector_type(2)));
-
-static inline int gcheck(hipError_t e) { return (int)e; }
-
-// Runtime flag -> template argument: f(std::true_type{}) or
-// f(std::false_type{}); nest one call per flag.
-template <typename F>
-static void with_bool(bool b, F&& f) {
-  if (b) f(std::true_type{});
-  else f(std::false_type{});
-}
 
 template <typename T> struct GemmCfg;
 template <> struct GemmCfg<float> {
@@ -215,7 +197,7 @@ __device__ __forceinline__ void emit(T& dst, T v) {
 // Staging: 16-byte vector loads (scalar, zero-padded at the edges when
 // GUARD); A is transposed on its way into LDS.
 template <typename T, bool ACC, bool GUARD>
-__global__ void __launch_bounds__(GBLK) gemm_kernel(
+__global__ void __launch_bounds__(BLK) gemm_kernel(
     const T* __restrict__ A, const T* __restrict__ B, T* __restrict__ C,
     int64_t M, int64_t N, int64_t K, int64_t lda, int64_t ldb, int64_t ldc) {
   using CFG = GemmCfg<T>;
@@ -239,14 +221,14 @@ __global__ void __launch_bounds__(GBLK) gemm_kernel(
 
   typename CFG::acc_t acc[1][MI][NJ] = {};
 
-  constexpr int AV = (BM * BK) / VW / GBLK;  // A vector loads per thread
-  constexpr int BV = (BK * BN) / VW / GBLK;  // B vector loads per thread
+  constexpr int AV = (BM * BK) / VW / BLK;  // A vector loads per thread
+  constexpr int BV = (BK * BN) / VW / BLK;  // B vector loads per thread
   vec_t areg[AV], breg[BV];
 
   auto load_panel = [&](int64_t k0) {
 #pragma unroll
     for (int e = 0; e < AV; ++e) {
-      const int vi = tid + GBLK * e;
+      const int vi = tid + BLK * e;
       const int row = vi / (BK / VW);
       const int kv = vi % (BK / VW);
       const int64_t gr = brow + row;
@@ -263,7 +245,7 @@ __global__ void __launch_bounds__(GBLK) gemm_kernel(
     }
 #pragma unroll
     for (int e = 0; e < BV; ++e) {
-      const int vi = tid + GBLK * e;
+      const int vi = tid + BLK * e;
       const int kb = vi / (BN / VW);
       const int nv = vi % (BN / VW);
       const int64_t gk = k0 + kb;
@@ -281,7 +263,7 @@ __global__ void __launch_bounds__(GBLK) gemm_kernel(
   auto store_panel = [&](int buf) {
 #pragma unroll
     for (int e = 0; e < AV; ++e) {
-      const int vi = tid + GBLK * e;
+      const int vi = tid + BLK * e;
       const int row = vi / (BK / VW);
       const int kv = vi % (BK / VW);
 #pragma unroll
@@ -289,7 +271,7 @@ __global__ void __launch_bounds__(GBLK) gemm_kernel(
     }
 #pragma unroll
     for (int e = 0; e < BV; ++e) {
-      const int vi = tid + GBLK * e;
+      const int vi = tid + BLK * e;
       const int kb = vi / (BN / VW);
       const int nv = vi % (BN / VW);
       *reinterpret_cast<vec_t*>(&Bs[0][buf][kb][nv * VW]) = breg[e];
@@ -320,12 +302,12 @@ static int gemm_launch(void* stream, const void* A, const void* B, void* C,
                        (K % CFG::BK == 0);
   with_bool(accumulate, [&](auto acc) {
     with_bool(!aligned, [&](auto guard) {
-      hipLaunchKernelGGL((gemm_kernel<T, acc(), guard()>), grid, dim3(GBLK),
+      hipLaunchKernelGGL((gemm_kernel<T, acc(), guard()>), grid, dim3(BLK),
                          0, (hipStream_t)stream, (const T*)A, (const T*)B,
                          (T*)C, M, N, K, lda, ldb, ldc);
     });
   });
-  return gcheck(hipGetLastError());
+  return check(hipGetLastError());
 }
 
 extern "C" int pam_gemm(void* stream, const void* A, const void* B, void* C,
@@ -359,7 +341,7 @@ extern "C" int pam_gemm(void* stream, const void* A, const void* B, void* C,
 // matrix-core rate.
 // ---------------------------------------------------------------------------
 template <typename T, int NPL, bool CT, bool ACC, int BK>
-__global__ void __launch_bounds__(GBLK) gemm_batched_kernel(
+__global__ void __launch_bounds__(BLK) gemm_batched_kernel(
     const T* __restrict__ A, const T* __restrict__ B, T* __restrict__ C,
     int64_t M, int64_t N, int64_t K, int64_t strideA, int64_t strideB,
     int64_t strideC) {
@@ -388,14 +370,14 @@ __global__ void __launch_bounds__(GBLK) gemm_batched_kernel(
 
   typename CFG::acc_t acc[NPL * NPL][MI][NJ] = {};
 
-  constexpr int AE = (BM * BK) / GBLK;
-  constexpr int BE = (BK * BN) / GBLK;
+  constexpr int AE = (BM * BK) / BLK;
+  constexpr int BE = (BK * BN) / BLK;
   T areg[AE][NPL], breg[BE][NPL];
 
   // element e of this thread in the A panel -> (k, m); consecutive threads
   // follow the contiguous direction of A: m when A is [K, M] (CT), else k
   auto a_km = [&](int e, int& kk, int& mm) {
-    const int v = ln.tid + GBLK * e;
+    const int v = ln.tid + BLK * e;
     if constexpr (CT) {
       mm = v & (BM - 1);
       kk = v / BM;
@@ -425,7 +407,7 @@ __global__ void __launch_bounds__(GBLK) gemm_batched_kernel(
     }
 #pragma unroll
     for (int e = 0; e < BE; ++e) {
-      const int v = ln.tid + GBLK * e;
+      const int v = ln.tid + BLK * e;
       const int64_t gk = k0 + v / BN;
       const int64_t gn = n0 + (v & (BN - 1));
 #pragma unroll
@@ -445,7 +427,7 @@ __global__ void __launch_bounds__(GBLK) gemm_batched_kernel(
     }
 #pragma unroll
     for (int e = 0; e < BE; ++e) {
-      const int v = ln.tid + GBLK * e;
+      const int v = ln.tid + BLK * e;
 #pragma unroll
       for (int pl = 0; pl < NPL; ++pl)
         Bs[pl][buf][v / BN][v & (BN - 1)] = breg[e][pl];
@@ -475,10 +457,7 @@ __global__ void __launch_bounds__(GBLK) gemm_batched_kernel(
 // (0.207->0.218), so K<=64 auto-selects BK=8; PAM_CGEMM_BK=8 / 16 (read
 // once per process) forces the shallow / the deep panel.
 static int cgemm_bk(int64_t K) {
-  static const int bkov = [] {
-    const char* e = getenv("PAM_CGEMM_BK");
-    return e ? atoi(e) : 0;
-  }();
+  static const int bkov = (int)env_int("PAM_CGEMM_BK", 0);
   return (bkov == 8 || (bkov == 0 && K <= 64)) ? 8 : 16;
 }
 
@@ -493,7 +472,7 @@ static int batched_launch(void* stream, const void* A, const void* B, void* C,
             (uint32_t)batch);
   auto launch = [&](auto ct, auto ac, auto bk) {
     hipLaunchKernelGGL((gemm_batched_kernel<T, NPL, ct(), ac(), bk()>), grid,
-                       dim3(GBLK), 0, (hipStream_t)stream, (const T*)A,
+                       dim3(BLK), 0, (hipStream_t)stream, (const T*)A,
                        (const T*)B, (T*)C, M, N, K, sA, sB, sC);
   };
   using BK8 = std::integral_constant<int, 8>;
@@ -507,7 +486,7 @@ static int batched_launch(void* stream, const void* A, const void* B, void* C,
     }
     with_bool(acc, [&](auto ac) { launch(ct, ac, BK16{}); });
   });
-  return gcheck(hipGetLastError());
+  return check(hipGetLastError());
 }
 
 extern "C" int pam_cgemm_batched(void* stream, const void* A, const void* B,
@@ -545,7 +524,7 @@ extern "C" int pam_gemm_batched(void* stream, const void* A, const void* B,
 // 32x32 tiles, +1 pad against bank conflicts.
 // ---------------------------------------------------------------------------
 template <typename T, int NV, bool CONJ>
-__global__ void __launch_bounds__(GBLK) transpose_kernel(
+__global__ void __launch_bounds__(BLK) transpose_kernel(
     const T* __restrict__ A, T* __restrict__ At, int64_t nr, int64_t nc) {
   __shared__ T tile[32][33][NV];
   const int64_t r0 = (int64_t)blockIdx.y * 32;
@@ -578,9 +557,9 @@ template <typename T, int NV, bool CONJ = false>
 static int transpose_launch(void* stream, const void* A, void* At, int64_t nr,
                             int64_t nc) {
   dim3 grid((uint32_t)((nc + 31) / 32), (uint32_t)((nr + 31) / 32));
-  hipLaunchKernelGGL((transpose_kernel<T, NV, CONJ>), grid, dim3(GBLK), 0,
+  hipLaunchKernelGGL((transpose_kernel<T, NV, CONJ>), grid, dim3(BLK), 0,
                      (hipStream_t)stream, (const T*)A, (T*)At, nr, nc);
-  return gcheck(hipGetLastError());
+  return check(hipGetLastError());
 }
 
 extern "C" int pam_ctranspose(void* stream, const void* A, void* At,

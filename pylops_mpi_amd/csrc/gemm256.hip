@@ -20,17 +20,12 @@
 // Preconditions (fast path only — caller falls back to pam_gemm):
 // M % 256 == 0, N % 256 == 0, K % 32 == 0, 16-byte aligned pointers.
 
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-
-#include "../../include/pam.h"
-
-#define G256_BLK 256
+#include "launch.h"
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 template <bool ACC>
-__global__ void __launch_bounds__(G256_BLK, 1) gemm256_f32_kernel(
+__global__ void __launch_bounds__(BLK, 1) gemm256_f32_kernel(
     const float* __restrict__ At, const float* __restrict__ B,
     float* __restrict__ C, int64_t M, int64_t N, int64_t K) {
   constexpr int BM = 256, BN = 256, BK = 32;
@@ -152,11 +147,11 @@ extern "C" int pam_gemm_kt(void* stream, const void* At, const void* B,
   dim3 grid((uint32_t)(N / 256), (uint32_t)(M / 256));
   hipStream_t s = (hipStream_t)stream;
   if (accumulate)
-    hipLaunchKernelGGL((gemm256_f32_kernel<true>), grid, dim3(G256_BLK), 0,
+    hipLaunchKernelGGL((gemm256_f32_kernel<true>), grid, dim3(BLK), 0,
                        s, (const float*)At, (const float*)B, (float*)C, M,
                        N, K);
   else
-    hipLaunchKernelGGL((gemm256_f32_kernel<false>), grid, dim3(G256_BLK), 0,
+    hipLaunchKernelGGL((gemm256_f32_kernel<false>), grid, dim3(BLK), 0,
                        s, (const float*)At, (const float*)B, (float*)C, M,
                        N, K);
   return (int)hipGetLastError();

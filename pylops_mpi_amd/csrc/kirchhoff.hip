@@ -44,17 +44,12 @@
 // schedule, so the forward is not pinned bit for bit: a sample is the sum of
 // its n rounded products in some order.
 
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-#include <stdlib.h>
-
-#include "../../include/pam.h"
+#include "launch.h"
 
 #pragma clang fp contract(off)
 
-#define KBLK 256
 #define KIRCH_R 4                    // image points per thread, adjoint
-#define KIRCH_P (KBLK * KIRCH_R)     // image points per workgroup, adjoint
+#define KIRCH_P (BLK * KIRCH_R)     // image points per workgroup, adjoint
 #define KIRCH_CHUNK 32               // traces per partial when traces split
 #define KIRCH_LDS_BYTES 65536        // LDS budget of one workgroup
 #define KIRCH_FILL 512               // workgroups that fill the chip (2 / CU)
@@ -72,7 +67,7 @@
 
 // ---------------------------------------------------------------- adjoint
 template <typename T, bool STAGE>
-__global__ void __launch_bounds__(KBLK) kirch_gather_kernel(
+__global__ void __launch_bounds__(BLK) kirch_gather_kernel(
     const T* __restrict__ d, T* __restrict__ out, const T* __restrict__ qs,
     const T* __restrict__ qr, int64_t nr, int64_t ntr, int64_t ni,
     int64_t nt, int64_t chunk, int64_t ntile, int64_t nitems) {
@@ -93,14 +88,14 @@ __global__ void __launch_bounds__(KBLK) kirch_gather_kernel(
       const T* dk = d + k * nt;
       if constexpr (STAGE) {
         __syncthreads();      // the previous trace has been read
-        for (int64_t j = tid; j < nt; j += KBLK) lds[j] = dk[j];
+        for (int64_t j = tid; j < nt; j += BLK) lds[j] = dk[j];
         __syncthreads();
       }
       const T* qsk = qs + is * ni;
       const T* qrk = qr + ir * ni;
 #pragma unroll
       for (int r = 0; r < KIRCH_R; ++r) {
-        const int64_t i = i0 + (int64_t)r * KBLK;
+        const int64_t i = i0 + (int64_t)r * BLK;
         if (i < ni) {
           const T q = qsk[i] + qrk[i];
           if (q >= (T)0 && q < tmax) {
@@ -130,7 +125,7 @@ __global__ void __launch_bounds__(KBLK) kirch_gather_kernel(
     T* o = out + c * ni;    // the image itself when there is one chunk
 #pragma unroll
     for (int r = 0; r < KIRCH_R; ++r) {
-      const int64_t i = i0 + (int64_t)r * KBLK;
+      const int64_t i = i0 + (int64_t)r * BLK;
       if (i < ni) o[i] = acc[r];
     }
   }
@@ -138,11 +133,11 @@ __global__ void __launch_bounds__(KBLK) kirch_gather_kernel(
 
 // mig[i] = ws[0, i] + ws[1, i] + ... in ascending chunk order
 template <typename T>
-__global__ void __launch_bounds__(KBLK) kirch_combine_kernel(
+__global__ void __launch_bounds__(BLK) kirch_combine_kernel(
     const T* __restrict__ ws, T* __restrict__ mig, int64_t ni,
     int64_t nchunk) {
-  const int64_t stride = (int64_t)gridDim.x * KBLK;
-  for (int64_t i = (int64_t)blockIdx.x * KBLK + threadIdx.x; i < ni;
+  const int64_t stride = (int64_t)gridDim.x * BLK;
+  for (int64_t i = (int64_t)blockIdx.x * BLK + threadIdx.x; i < ni;
        i += stride) {
     T acc = ws[i];
     for (int64_t c = 1; c < nchunk; ++c) acc += ws[c * ni + i];
@@ -156,7 +151,7 @@ __global__ void __launch_bounds__(KBLK) kirch_combine_kernel(
 // 134 Mpair shape of profiles/kirchhoff.log).  The products are rounded in
 // T; the sum is rounded to T once, when the window is written.
 template <typename T>
-__global__ void __launch_bounds__(KBLK) kirch_spread_kernel(
+__global__ void __launch_bounds__(BLK) kirch_spread_kernel(
     const T* __restrict__ m, T* __restrict__ d, const T* __restrict__ qs,
     const T* __restrict__ qr, int64_t nr, int64_t ni, int64_t nt, int64_t W,
     int64_t nwin, int64_t nitems) {
@@ -171,9 +166,9 @@ __global__ void __launch_bounds__(KBLK) kirch_spread_kernel(
     const int64_t is = k / nr, ir = k - is * nr;
     const T* qsk = qs + is * ni;
     const T* qrk = qr + ir * ni;
-    for (int64_t j = tid; j < wl; j += KBLK) lds[j] = 0.0;
+    for (int64_t j = tid; j < wl; j += BLK) lds[j] = 0.0;
     __syncthreads();
-    for (int64_t i = tid; i < ni; i += KBLK) {
+    for (int64_t i = tid; i < ni; i += BLK) {
       const T q = qsk[i] + qrk[i];
       if (q >= (T)0 && q < tmax) {
         const T f = floor(q);
@@ -190,17 +185,13 @@ __global__ void __launch_bounds__(KBLK) kirch_spread_kernel(
     }
     __syncthreads();
     T* dk = d + k * nt + t0;
-    for (int64_t j = tid; j < wl; j += KBLK) dk[j] = (T)lds[j];
+    for (int64_t j = tid; j < wl; j += BLK) dk[j] = (T)lds[j];
     __syncthreads();        // the window is reused by the next item
   }
 }
 
 // ------------------------------------------------------------ launch plan
-static int64_t kirch_env(const char* name) {  // read on EVERY call
-  const char* e = getenv(name);
-  return (e && *e) ? atoll(e) : -1;
-}
-
+// (the PAM_KIRCH_* knobs are read on EVERY call)
 static int64_t kirch_tsize(int dtype) { return dtype == PAM_F64 ? 8 : 4; }
 
 // forward window: PAM_KIRCH_WINDOW = W in [1, budget] forces it; else the
@@ -208,7 +199,7 @@ static int64_t kirch_tsize(int dtype) { return dtype == PAM_F64 ? 8 : 4; }
 // least KIRCH_W_MIN and at most the LDS budget; never longer than nt
 static int64_t kirch_window_of(int64_t ntr, int64_t nt) {
   const int64_t wmax = KIRCH_LDS_BYTES / (int64_t)sizeof(double);
-  int64_t W = kirch_env("PAM_KIRCH_WINDOW");
+  int64_t W = env_int("PAM_KIRCH_WINDOW", -1);
   if (W < 1 || W > wmax) {
     const int64_t want = ntr >= KIRCH_FILL ? 1 : (KIRCH_FILL + ntr - 1) / ntr;
     W = (nt + want - 1) / want;
@@ -235,13 +226,13 @@ static KirchAdjPlan kirch_adj_plan(int dtype, int64_t ntr, int64_t ni,
   KirchAdjPlan P;
   P.ntile = (ni + KIRCH_P - 1) / KIRCH_P;
   const int64_t nck = (ntr + KIRCH_CHUNK - 1) / KIRCH_CHUNK;
-  const int64_t forced = kirch_env("PAM_KIRCH_SPLIT");
+  const int64_t forced = env_int("PAM_KIRCH_SPLIT", -1);
   bool split = P.ntile < KIRCH_FILL && nck <= KIRCH_WS_MAX / ni;
   if (forced == 0 || forced == 1) split = forced == 1;
   split = split && nck > 1;
   P.chunk = split ? KIRCH_CHUNK : ntr;
   P.nchunk = split ? nck : 1;
-  const int64_t st = kirch_env("PAM_KIRCH_STAGE");
+  const int64_t st = env_int("PAM_KIRCH_STAGE", -1);
   P.stage = (st == 0 || st == 1) ? (int)st : KIRCH_STAGE_AUTO;
   if (nt > KIRCH_LDS_BYTES / kirch_tsize(dtype)) P.stage = 0;
   return P;
@@ -300,7 +291,7 @@ static int kirch_launch(hipStream_t s, int adjoint, void* m, void* d,
     const int64_t nwin = (nt + W - 1) / W;
     const int64_t nitems = ntr * nwin;
     hipLaunchKernelGGL((kirch_spread_kernel<T>), dim3(kirch_grid(nitems)),
-                       dim3(KBLK), (size_t)(W * sizeof(double)), s, (const T*)m,
+                       dim3(BLK), (size_t)(W * sizeof(double)), s, (const T*)m,
                        (T*)d, qsp, qrp, nr, ni, nt, W, nwin, nitems);
     return (int)hipGetLastError();
   }
@@ -309,20 +300,20 @@ static int kirch_launch(hipStream_t s, int adjoint, void* m, void* d,
   T* out = P.nchunk > 1 ? (T*)ws : (T*)m;
   if (P.stage)
     hipLaunchKernelGGL((kirch_gather_kernel<T, true>),
-                       dim3(kirch_grid(nitems)), dim3(KBLK),
+                       dim3(kirch_grid(nitems)), dim3(BLK),
                        (size_t)(nt * sizeof(T)), s, (const T*)d, out, qsp,
                        qrp, nr, ntr, ni, nt, P.chunk, P.ntile, nitems);
   else
     hipLaunchKernelGGL((kirch_gather_kernel<T, false>),
-                       dim3(kirch_grid(nitems)), dim3(KBLK), 0, s,
+                       dim3(kirch_grid(nitems)), dim3(BLK), 0, s,
                        (const T*)d, out, qsp, qrp, nr, ntr, ni, nt, P.chunk,
                        P.ntile, nitems);
   int rc = (int)hipGetLastError();
   if (rc || P.nchunk == 1) return rc;
-  int64_t g = (ni + KBLK - 1) / KBLK;
+  int64_t g = (ni + BLK - 1) / BLK;
   if (g > 4096) g = 4096;
   hipLaunchKernelGGL((kirch_combine_kernel<T>), dim3((unsigned)g),
-                     dim3(KBLK), 0, s, (const T*)ws, (T*)m, ni, P.nchunk);
+                     dim3(BLK), 0, s, (const T*)ws, (T*)m, ni, P.nchunk);
   return (int)hipGetLastError();
 }
 

@@ -7,6 +7,11 @@
 //    shapes differ by family: element-wise kernels run one block per 256
 //    vector items with no stride loop (grid_1d), reductions a fixed grid of
 //    at most NPARTIAL grid-stride blocks, stencils the grid fd_plan picks.
+//  * The vector primitives launch through three shared pieces: the
+//    dispatchers of launch.h turn dtype, op, kind, ncomp and flags into
+//    template arguments, vec_launch is the one "16-byte aligned -> V =
+//    VecW<T>, else V = 1" fork, and reduce_launch is the one two-stage
+//    deterministic reduction (dot, cdot, norms, group norm).
 //  * The finite-difference stencils are FUSED: one pass, reading the
 //    neighbour halo planes directly from small exchange buffers instead of
 //    materializing a concatenated ghosted copy the way the reference does
@@ -22,23 +27,23 @@
 //    n (grid-stride per-thread accumulation -> 64-lane __shfl_down wave
 //    reduction -> LDS tree -> fixed-size partial buffer -> one-block
 //    deterministic combine), so CGLS traces are reproducible run-to-run.
+//    An empty reduction (n == 0) is the combine over zero partials: the
+//    result is written by a kernel on the caller's stream, never by a
+//    host copy.
 //
 // Build: hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off
 //        -fPIC -shared pam.hip -o ../libpam.so
 // (-ffp-contract=off: keep mul+add roundings separate so results track the
 //  reference NumPy op-for-op at the ulp level.)
 
-#include <hip/hip_runtime.h>
 #include <math.h>
-#include <stdint.h>
-#include <stdlib.h>
-#include <utility>
 
-#include "../../include/pam.h"
+#include <initializer_list>
+
+#include "launch.h"
 #include "fd_defs.h"
 
 #define PAM_ABI_VERSION 1
-#define BLK 256
 #define NPARTIAL 1024  // fixed stage-1 partial count cap (determinism)
 
 extern "C" int64_t pam_version(void) { return PAM_ABI_VERSION; }
@@ -47,8 +52,6 @@ extern "C" int64_t pam_reduce_ws_elems(void) { return NPARTIAL; }
 // ---------------------------------------------------------------------------
 // helpers
 // ---------------------------------------------------------------------------
-static inline int check(hipError_t e) { return (int)e; }
-
 static inline int64_t grid_1d(int64_t work) {
   // One block per BLK work items — NO grid-stride looping by default.
   // A/B at the bench size (fp64 axpy, single box): cap=4096 (the old
@@ -56,21 +59,54 @@ static inline int64_t grid_1d(int64_t work) {
   // (+28%) — the stride loop was the bottleneck, not launch width.
   // (The deterministic dot/norm reductions are unaffected: their
   // stage-1 grid is the fixed NPARTIAL tree, not grid_1d.)
-  // PAM_EW_CAP restores a cap for A/Bs.
-  static int64_t cap = [] {
-    const char* e = getenv("PAM_EW_CAP");
-    return (int64_t)(e ? atoll(e) : 0x7FFFFFFF);
-  }();
+  // PAM_EW_CAP (read once per process) restores a cap for A/Bs.
+  static const int64_t cap = env_int("PAM_EW_CAP", 0x7FFFFFFF);
   int64_t g = (work + BLK - 1) / BLK;
   if (g > cap) g = cap;
   if (g < 1) g = 1;
   return g;
 }
 
+// The one vector-or-scalar fork.  Calls f(std::integral_constant<int, V>{})
+// with V = VecW<T> (one 16-byte vector per item) when `ok` holds and every
+// pointer of `ptrs` is 16-byte aligned (NULL is), else with V = 1; f
+// launches and the launch's error code is returned.  The grid is f's to
+// choose: the families derive theirs from V in different ways.
+template <typename T, typename F>
+static int vec_launch(bool ok, std::initializer_list<const void*> ptrs,
+                      F&& f) {
+  for (const void* p : ptrs) ok = ok && (uintptr_t)p % 16 == 0;
+  if (ok) f(std::integral_constant<int, VecW<T>::value>{});
+  else f(std::integral_constant<int, 1>{});
+  return check(hipGetLastError());
+}
+
 // ---------------------------------------------------------------------------
 // element-wise kernels (ref DistributedArray.py:605-683 local math)
 // EW op codes: 0 fill, 1 neg, 2 add, 3 sub, 4 mul, 5 scale, 6 axpy, 7 xpby
 // ---------------------------------------------------------------------------
+// one work item: V elements at offset off (a 16-byte vector, or one element)
+template <typename T, int OP, int V>
+__device__ __forceinline__ void ew_item(T* y, const T* a, const T* b,
+                                        T alpha, int64_t off) {
+  T va[V], vb[V], vy[V];
+  if constexpr (OP != 0) loadv<T, V>(a + off, va);            // all but fill
+  if constexpr (OP >= 2 && OP <= 4) loadv<T, V>(b + off, vb);  // binary a,b
+  if constexpr (OP >= 6) loadv<T, V>(y + off, vy);             // y & a
+#pragma unroll
+  for (int k = 0; k < V; ++k) {
+    if constexpr (OP == 0) vy[k] = alpha;
+    else if constexpr (OP == 1) vy[k] = -va[k];
+    else if constexpr (OP == 2) vy[k] = va[k] + vb[k];
+    else if constexpr (OP == 3) vy[k] = va[k] - vb[k];
+    else if constexpr (OP == 4) vy[k] = va[k] * vb[k];
+    else if constexpr (OP == 5) vy[k] = alpha * va[k];
+    else if constexpr (OP == 6) vy[k] = vy[k] + alpha * va[k];
+    else if constexpr (OP == 7) vy[k] = va[k] + alpha * vy[k];
+  }
+  storev<T, V>(y + off, vy);
+}
+
 template <typename T, int OP, int V>
 __device__ __forceinline__ void ew_body(T* __restrict__ y,
                                         const T* __restrict__ a,
@@ -78,47 +114,11 @@ __device__ __forceinline__ void ew_body(T* __restrict__ y,
                                         T alpha, int64_t n) {
   const int64_t nv = n / V;
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nv;
-       i += stride) {
-    T va[V], vb[V], vy[V];
-    if constexpr (OP == 1 || OP == 5) {  // unary on a
-      loadv<T, V>(a + i * V, va);
-    } else if constexpr (OP >= 2 && OP <= 4) {  // binary a,b
-      loadv<T, V>(a + i * V, va);
-      loadv<T, V>(b + i * V, vb);
-    } else if constexpr (OP == 6 || OP == 7) {  // y & a
-      loadv<T, V>(a + i * V, va);
-      loadv<T, V>(y + i * V, vy);
-    }
-#pragma unroll
-    for (int k = 0; k < V; ++k) {
-      if constexpr (OP == 0) vy[k] = alpha;
-      else if constexpr (OP == 1) vy[k] = -va[k];
-      else if constexpr (OP == 2) vy[k] = va[k] + vb[k];
-      else if constexpr (OP == 3) vy[k] = va[k] - vb[k];
-      else if constexpr (OP == 4) vy[k] = va[k] * vb[k];
-      else if constexpr (OP == 5) vy[k] = alpha * va[k];
-      else if constexpr (OP == 6) vy[k] = vy[k] + alpha * va[k];
-      else if constexpr (OP == 7) vy[k] = va[k] + alpha * vy[k];
-    }
-    storev<T, V>(y + i * V, vy);
-  }
-  // scalar tail
-  const int64_t tail0 = nv * V;
   const int64_t gid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  for (int64_t i = tail0 + gid; i < n; i += stride) {
-    T va = 0, vb = 0;
-    if constexpr (OP != 0) va = a[i];
-    if constexpr (OP >= 2 && OP <= 4) vb = b[i];
-    if constexpr (OP == 0) y[i] = alpha;
-    else if constexpr (OP == 1) y[i] = -va;
-    else if constexpr (OP == 2) y[i] = va + vb;
-    else if constexpr (OP == 3) y[i] = va - vb;
-    else if constexpr (OP == 4) y[i] = va * vb;
-    else if constexpr (OP == 5) y[i] = alpha * va;
-    else if constexpr (OP == 6) y[i] = y[i] + alpha * va;
-    else if constexpr (OP == 7) y[i] = va + alpha * y[i];
-  }
+  for (int64_t i = gid; i < nv; i += stride)
+    ew_item<T, OP, V>(y, a, b, alpha, i * V);
+  for (int64_t i = nv * V + gid; i < n; i += stride)  // scalar tail
+    ew_item<T, OP, 1>(y, a, b, alpha, i);
 }
 
 template <typename T, int OP, int V>
@@ -142,57 +142,64 @@ __global__ void __launch_bounds__(BLK) ewd_kernel(T* __restrict__ y,
   ew_body<T, OP, V>(y, a, nullptr, (T)(scale * ap[0]), n);
 }
 
-template <typename T, int OP>
-static int ew_launch(void* stream, void* y, const void* a, const void* b,
-                     double alpha, int64_t n) {
-  if (n < 0) return PAM_EARG;
-  if (n == 0) return 0;
-  constexpr int V = VecW<T>::value;
-  const bool aligned = ((uintptr_t)y % 16 == 0) &&
-                       (a == nullptr || (uintptr_t)a % 16 == 0) &&
-                       (b == nullptr || (uintptr_t)b % 16 == 0);
-  hipStream_t s = (hipStream_t)stream;
-  const int64_t grid = grid_1d(n / (aligned ? V : 1) + 1);
-  if (aligned)
-    hipLaunchKernelGGL((ew_kernel<T, OP, V>), dim3(grid), dim3(BLK), 0, s,
-                       (T*)y, (const T*)a, (const T*)b, (T)alpha, n);
-  else
-    hipLaunchKernelGGL((ew_kernel<T, OP, 1>), dim3(grid), dim3(BLK), 0, s,
-                       (T*)y, (const T*)a, (const T*)b, (T)alpha, n);
-  return check(hipGetLastError());
+// Every element-wise entry point.  DEV: alpha = scale * *ap with ap on the
+// device (ewd_kernel), and y, a, ap must not be NULL once n > 0 (an empty
+// block has no storage: its pointers may be NULL).
+template <int OP, bool DEV = false>
+static int ew_launch(int dtype, void* stream, void* y, const void* a,
+                     const void* b, const void* ap, double alpha, int64_t n) {
+  return with_real(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    if (n < 0) return PAM_EARG;
+    if (n == 0) return 0;
+    if (DEV && (!y || !a || !ap)) return PAM_EARG;
+    return vec_launch<T>(true, {y, a, b}, [&](auto v) {
+      constexpr int V = decltype(v)::value;
+      const dim3 grid((uint32_t)grid_1d(n / V + 1));
+      if constexpr (DEV)
+        hipLaunchKernelGGL((ewd_kernel<T, OP, V>), grid, dim3(BLK), 0,
+                           (hipStream_t)stream, (T*)y, (const T*)a,
+                           (const double*)ap, alpha, n);
+      else
+        hipLaunchKernelGGL((ew_kernel<T, OP, V>), grid, dim3(BLK), 0,
+                           (hipStream_t)stream, (T*)y, (const T*)a,
+                           (const T*)b, (T)alpha, n);
+    });
+  });
 }
 
-#define EW_ENTRY(name, OP, A, B, ALPHA)                                       \
-  extern "C" int name {                                                       \
-    if (dtype == PAM_F64)                                                     \
-      return ew_launch<double, OP>(stream, y, A, B, ALPHA, n);                \
-    if (dtype == PAM_F32)                                                     \
-      return ew_launch<float, OP>(stream, y, A, B, ALPHA, n);                 \
-    return PAM_EDTYPE;                                                        \
-  }
-
-EW_ENTRY(pam_fill(void* stream, void* y, int64_t n, double value, int dtype),
-         0, nullptr, nullptr, value)
-EW_ENTRY(pam_neg(void* stream, void* y, const void* x, int64_t n, int dtype),
-         1, x, nullptr, 0.0)
-EW_ENTRY(pam_add(void* stream, void* y, const void* a, const void* b,
-                 int64_t n, int dtype),
-         2, a, b, 0.0)
-EW_ENTRY(pam_sub(void* stream, void* y, const void* a, const void* b,
-                 int64_t n, int dtype),
-         3, a, b, 0.0)
-EW_ENTRY(pam_mul(void* stream, void* y, const void* a, const void* b,
-                 int64_t n, int dtype),
-         4, a, b, 0.0)
-EW_ENTRY(pam_scale(void* stream, void* y, const void* x, double alpha,
-                   int64_t n, int dtype),
-         5, x, nullptr, alpha)
-EW_ENTRY(pam_axpy(void* stream, void* y, const void* x, double alpha,
-                  int64_t n, int dtype),
-         6, x, nullptr, alpha)
-EW_ENTRY(pam_xpby(void* stream, void* y, const void* x, double beta,
-                  int64_t n, int dtype),
-         7, x, nullptr, beta)
+extern "C" int pam_fill(void* stream, void* y, int64_t n, double value,
+                        int dtype) {
+  return ew_launch<0>(dtype, stream, y, nullptr, nullptr, nullptr, value, n);
+}
+extern "C" int pam_neg(void* stream, void* y, const void* x, int64_t n,
+                       int dtype) {
+  return ew_launch<1>(dtype, stream, y, x, nullptr, nullptr, 0.0, n);
+}
+extern "C" int pam_add(void* stream, void* y, const void* a, const void* b,
+                       int64_t n, int dtype) {
+  return ew_launch<2>(dtype, stream, y, a, b, nullptr, 0.0, n);
+}
+extern "C" int pam_sub(void* stream, void* y, const void* a, const void* b,
+                       int64_t n, int dtype) {
+  return ew_launch<3>(dtype, stream, y, a, b, nullptr, 0.0, n);
+}
+extern "C" int pam_mul(void* stream, void* y, const void* a, const void* b,
+                       int64_t n, int dtype) {
+  return ew_launch<4>(dtype, stream, y, a, b, nullptr, 0.0, n);
+}
+extern "C" int pam_scale(void* stream, void* y, const void* x, double alpha,
+                         int64_t n, int dtype) {
+  return ew_launch<5>(dtype, stream, y, x, nullptr, nullptr, alpha, n);
+}
+extern "C" int pam_axpy(void* stream, void* y, const void* x, double alpha,
+                        int64_t n, int dtype) {
+  return ew_launch<6>(dtype, stream, y, x, nullptr, nullptr, alpha, n);
+}
+extern "C" int pam_xpby(void* stream, void* y, const void* x, double beta,
+                        int64_t n, int dtype) {
+  return ew_launch<7>(dtype, stream, y, x, nullptr, nullptr, beta, n);
+}
 
 // ---------------------------------------------------------------------------
 // device-scalar solver fast path (ref optimization/cls_basic.py:370-404):
@@ -200,42 +207,18 @@ EW_ENTRY(pam_xpby(void* stream, void* y, const void* x, double beta,
 // recurrence-scalar kernels.  Together these let a whole CG/CGLS iteration
 // be launched with a single host synchronization (the stop-test readback).
 // ---------------------------------------------------------------------------
-template <typename T, int OP>
-static int ewd_launch(void* stream, void* y, const void* a, const void* ap,
-                      double scale, int64_t n) {
-  if (n < 0) return PAM_EARG;
-  if (n == 0) return 0;  // an empty block has no storage: y, a may be NULL
-  if (!y || !a || !ap) return PAM_EARG;
-  constexpr int V = VecW<T>::value;
-  const bool aligned =
-      ((uintptr_t)y % 16 == 0) && ((uintptr_t)a % 16 == 0);
-  hipStream_t s = (hipStream_t)stream;
-  const int64_t grid = grid_1d(n / (aligned ? V : 1) + 1);
-  if (aligned)
-    hipLaunchKernelGGL((ewd_kernel<T, OP, V>), dim3(grid), dim3(BLK), 0, s,
-                       (T*)y, (const T*)a, (const double*)ap, scale, n);
-  else
-    hipLaunchKernelGGL((ewd_kernel<T, OP, 1>), dim3(grid), dim3(BLK), 0, s,
-                       (T*)y, (const T*)a, (const double*)ap, scale, n);
-  return check(hipGetLastError());
-}
-
 // y += scale * (*alpha) * x
 extern "C" int pam_axpy_d(void* stream, void* y, const void* x,
                           const void* alpha, double scale, int64_t n,
                           int dtype) {
-  if (dtype == PAM_F64) return ewd_launch<double, 6>(stream, y, x, alpha, scale, n);
-  if (dtype == PAM_F32) return ewd_launch<float, 6>(stream, y, x, alpha, scale, n);
-  return PAM_EDTYPE;
+  return ew_launch<6, true>(dtype, stream, y, x, nullptr, alpha, scale, n);
 }
 
 // y = x + scale * (*beta) * y
 extern "C" int pam_xpby_d(void* stream, void* y, const void* x,
                           const void* beta, double scale, int64_t n,
                           int dtype) {
-  if (dtype == PAM_F64) return ewd_launch<double, 7>(stream, y, x, beta, scale, n);
-  if (dtype == PAM_F32) return ewd_launch<float, 7>(stream, y, x, beta, scale, n);
-  return PAM_EDTYPE;
+  return ew_launch<7, true>(dtype, stream, y, x, nullptr, beta, scale, n);
 }
 
 // *out = |num[0] / (den[0] + damp * den[1])| — the CG/CGLS step scalars
@@ -305,35 +288,33 @@ __global__ void __launch_bounds__(BLK) ewc_kernel(T* __restrict__ y,
   }
 }
 
-template <typename T, int OP>
-static int ewc_launch(void* stream, void* y, const void* a, const void* b,
-                      double ar, double ai, int64_t n) {
-  if (n < 0) return PAM_EARG;
-  if (n == 0) return 0;
-  hipStream_t s = (hipStream_t)stream;
-  hipLaunchKernelGGL((ewc_kernel<T, OP>), dim3(grid_1d(n)), dim3(BLK), 0, s,
-                     (T*)y, (const T*)a, (const T*)b, (T)ar, (T)ai, n);
-  return check(hipGetLastError());
+template <int OP>
+static int ewc_launch(int dtype, void* stream, void* y, const void* a,
+                      const void* b, double ar, double ai, int64_t n) {
+  return with_cplx(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    if (n < 0) return PAM_EARG;
+    if (n == 0) return 0;
+    hipLaunchKernelGGL((ewc_kernel<T, OP>), dim3(grid_1d(n)), dim3(BLK), 0,
+                       (hipStream_t)stream, (T*)y, (const T*)a, (const T*)b,
+                       (T)ar, (T)ai, n);
+    return check(hipGetLastError());
+  });
 }
 
-#define EWC_ENTRY(name, OP, B, AR, AI)                                        \
-  extern "C" int name {                                                       \
-    if (dtype == PAM_C128)                                                    \
-      return ewc_launch<double, OP>(stream, y, a, B, AR, AI, n);              \
-    if (dtype == PAM_C64)                                                     \
-      return ewc_launch<float, OP>(stream, y, a, B, AR, AI, n);               \
-    return PAM_EDTYPE;                                                        \
-  }
-
-EWC_ENTRY(pam_cmul(void* stream, void* y, const void* a, const void* b,
-                   int64_t n, int dtype),
-          0, b, 0.0, 0.0)
-EWC_ENTRY(pam_cscale(void* stream, void* y, const void* a, double alpha_re,
-                     double alpha_im, int64_t n, int dtype),
-          1, nullptr, alpha_re, alpha_im)
-EWC_ENTRY(pam_conj(void* stream, void* y, const void* a, int64_t n,
-                   int dtype),
-          2, nullptr, 0.0, 0.0)
+extern "C" int pam_cmul(void* stream, void* y, const void* a, const void* b,
+                        int64_t n, int dtype) {
+  return ewc_launch<0>(dtype, stream, y, a, b, 0.0, 0.0, n);
+}
+extern "C" int pam_cscale(void* stream, void* y, const void* a,
+                          double alpha_re, double alpha_im, int64_t n,
+                          int dtype) {
+  return ewc_launch<1>(dtype, stream, y, a, nullptr, alpha_re, alpha_im, n);
+}
+extern "C" int pam_conj(void* stream, void* y, const void* a, int64_t n,
+                        int dtype) {
+  return ewc_launch<2>(dtype, stream, y, a, nullptr, 0.0, 0.0, n);
+}
 
 // ---------------------------------------------------------------------------
 // complex <-> real (de)interleave: the MDC chain's real extraction
@@ -386,51 +367,30 @@ __global__ void __launch_bounds__(BLK) zip_kernel(
   }
 }
 
-template <typename T>
-static int zip_launch(void* stream, void* dst, const void* src, int64_t n,
-                      bool unzip) {
-  if (n < 0) return PAM_EARG;
-  if (n == 0) return 0;  // empty arrays have no storage (NULL)
-  if (!dst || !src) return PAM_EARG;
-  constexpr int V = VecW<T>::value;
-  const bool aligned = ((uintptr_t)dst % 16 == 0) &&
-                       ((uintptr_t)src % 16 == 0);
-  hipStream_t s = (hipStream_t)stream;
-  const int64_t grid = grid_1d(n / (aligned ? V : 1) + 1);
-  if (unzip) {
-    if (aligned)
-      hipLaunchKernelGGL((unzip_kernel<T, V>), dim3(grid), dim3(BLK), 0, s,
-                         (T*)dst, (const T*)src, n);
-    else
-      hipLaunchKernelGGL((unzip_kernel<T, 1>), dim3(grid), dim3(BLK), 0, s,
-                         (T*)dst, (const T*)src, n);
-  } else {
-    if (aligned)
-      hipLaunchKernelGGL((zip_kernel<T, V>), dim3(grid), dim3(BLK), 0, s,
-                         (T*)dst, (const T*)src, n);
-    else
-      hipLaunchKernelGGL((zip_kernel<T, 1>), dim3(grid), dim3(BLK), 0, s,
-                         (T*)dst, (const T*)src, n);
-  }
-  return check(hipGetLastError());
+static int zip_launch(int dtype, void* stream, void* dst, const void* src,
+                      int64_t n, bool unzip) {
+  return with_cplx(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    if (n < 0) return PAM_EARG;
+    if (n == 0) return 0;  // empty arrays have no storage (NULL)
+    if (!dst || !src) return PAM_EARG;
+    return vec_launch<T>(true, {dst, src}, [&](auto v) {
+      constexpr int V = decltype(v)::value;
+      hipLaunchKernelGGL((unzip ? unzip_kernel<T, V> : zip_kernel<T, V>),
+                         dim3((uint32_t)grid_1d(n / V + 1)), dim3(BLK), 0,
+                         (hipStream_t)stream, (T*)dst, (const T*)src, n);
+    });
+  });
 }
 
 extern "C" int pam_unzip(void* stream, void* dst_real, const void* src_cplx,
                          int64_t n, int dtype) {
-  if (dtype == PAM_C128)
-    return zip_launch<double>(stream, dst_real, src_cplx, n, true);
-  if (dtype == PAM_C64)
-    return zip_launch<float>(stream, dst_real, src_cplx, n, true);
-  return PAM_EDTYPE;
+  return zip_launch(dtype, stream, dst_real, src_cplx, n, true);
 }
 
 extern "C" int pam_zip(void* stream, void* dst_cplx, const void* src_real,
                        int64_t n, int dtype) {
-  if (dtype == PAM_C128)
-    return zip_launch<double>(stream, dst_cplx, src_real, n, false);
-  if (dtype == PAM_C64)
-    return zip_launch<float>(stream, dst_cplx, src_real, n, false);
-  return PAM_EDTYPE;
+  return zip_launch(dtype, stream, dst_cplx, src_real, n, false);
 }
 
 // ---------------------------------------------------------------------------
@@ -492,41 +452,32 @@ __global__ void __launch_bounds__(BLK) zipT_kernel(
   }
 }
 
+// both directions: the tiles of the complex side's columns run along grid.x
+// for unzipT and along grid.y for zipT
+static int zip_t_launch(int dtype, void* stream, void* dst, const void* src,
+                        int64_t nt, int64_t m, bool unzip) {
+  if (nt <= 0 || m <= 0 || !dst || !src) return PAM_EARG;
+  const uint32_t gm = (uint32_t)((m + 31) / 32);
+  const uint32_t gt = (uint32_t)((nt + 31) / 32);
+  const dim3 grid = unzip ? dim3(gm, gt) : dim3(gt, gm);
+  return with_cplx(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    hipLaunchKernelGGL((unzip ? unzipT_kernel<T> : zipT_kernel<T>), grid,
+                       dim3(BLK), 0, (hipStream_t)stream, (T*)dst,
+                       (const T*)src, nt, m);
+    return check(hipGetLastError());
+  });
+}
+
 extern "C" int pam_unzip_t(void* stream, void* dst_real,
                            const void* src_cplx, int64_t nt, int64_t m,
                            int dtype) {
-  if (nt <= 0 || m <= 0 || !dst_real || !src_cplx) return PAM_EARG;
-  dim3 grid((uint32_t)((m + 31) / 32), (uint32_t)((nt + 31) / 32));
-  hipStream_t s = (hipStream_t)stream;
-  if (dtype == PAM_C128) {
-    hipLaunchKernelGGL((unzipT_kernel<double>), grid, dim3(BLK), 0, s,
-                       (double*)dst_real, (const double*)src_cplx, nt, m);
-    return check(hipGetLastError());
-  }
-  if (dtype == PAM_C64) {
-    hipLaunchKernelGGL((unzipT_kernel<float>), grid, dim3(BLK), 0, s,
-                       (float*)dst_real, (const float*)src_cplx, nt, m);
-    return check(hipGetLastError());
-  }
-  return PAM_EDTYPE;
+  return zip_t_launch(dtype, stream, dst_real, src_cplx, nt, m, true);
 }
 
 extern "C" int pam_zip_t(void* stream, void* dst_cplx, const void* src_real,
                          int64_t nt, int64_t m, int dtype) {
-  if (nt <= 0 || m <= 0 || !dst_cplx || !src_real) return PAM_EARG;
-  dim3 grid((uint32_t)((nt + 31) / 32), (uint32_t)((m + 31) / 32));
-  hipStream_t s = (hipStream_t)stream;
-  if (dtype == PAM_C128) {
-    hipLaunchKernelGGL((zipT_kernel<double>), grid, dim3(BLK), 0, s,
-                       (double*)dst_cplx, (const double*)src_real, nt, m);
-    return check(hipGetLastError());
-  }
-  if (dtype == PAM_C64) {
-    hipLaunchKernelGGL((zipT_kernel<float>), grid, dim3(BLK), 0, s,
-                       (float*)dst_cplx, (const float*)src_real, nt, m);
-    return check(hipGetLastError());
-  }
-  return PAM_EDTYPE;
+  return zip_t_launch(dtype, stream, dst_cplx, src_real, nt, m, false);
 }
 
 // ---------------------------------------------------------------------------
@@ -594,35 +545,20 @@ __global__ void __launch_bounds__(BLK) thresh_kernel(T* __restrict__ y,
   }
 }
 
-template <typename T, bool CPLX>
-static int thresh_launch(void* stream, void* y, const void* x, int kind,
-                         double t, int64_t n) {
-  if (n < 0) return PAM_EARG;
-  if (n == 0) return 0;
-  hipStream_t s = (hipStream_t)stream;
-  if (kind == 0)
-    hipLaunchKernelGGL((thresh_kernel<T, CPLX, 0>), dim3(grid_1d(n)),
-                       dim3(BLK), 0, s, (T*)y, (const T*)x, (T)t, n);
-  else if (kind == 1)
-    hipLaunchKernelGGL((thresh_kernel<T, CPLX, 1>), dim3(grid_1d(n)),
-                       dim3(BLK), 0, s, (T*)y, (const T*)x, (T)t, n);
-  else if (kind == 2)
-    hipLaunchKernelGGL((thresh_kernel<T, CPLX, 2>), dim3(grid_1d(n)),
-                       dim3(BLK), 0, s, (T*)y, (const T*)x, (T)t, n);
-  else
-    return PAM_EOP;
-  return check(hipGetLastError());
-}
-
 extern "C" int pam_thresh(void* stream, void* y, const void* x, int64_t n,
                           int kind, double thresh, int dtype) {
-  switch (dtype) {
-    case PAM_F64: return thresh_launch<double, false>(stream, y, x, kind, thresh, n);
-    case PAM_F32: return thresh_launch<float, false>(stream, y, x, kind, thresh, n);
-    case PAM_C128: return thresh_launch<double, true>(stream, y, x, kind, thresh, n);
-    case PAM_C64: return thresh_launch<float, true>(stream, y, x, kind, thresh, n);
-    default: return PAM_EDTYPE;
-  }
+  return with_dtype(dtype, [&](auto t, auto cplx) {
+    using T = typename decltype(t)::type;
+    constexpr bool CPLX = decltype(cplx)::value;
+    if (n < 0) return PAM_EARG;
+    if (n == 0) return 0;
+    return with_int<0, 2>(kind, PAM_EOP, [&](auto k) {
+      hipLaunchKernelGGL((thresh_kernel<T, CPLX, decltype(k)::value>),
+                         dim3(grid_1d(n)), dim3(BLK), 0, (hipStream_t)stream,
+                         (T*)y, (const T*)x, (T)thresh, n);
+      return check(hipGetLastError());
+    });
+  });
 }
 
 // ---------------------------------------------------------------------------
@@ -639,21 +575,29 @@ __device__ __forceinline__ double red_combine(double u, double v) {
   else return u + v;
 }
 
+// the value of an empty reduction: 0, 0, +inf, 0 for the norm ops
 template <int RED> __device__ __forceinline__ double red_init() {
   if constexpr (RED == 2) return 0.0;          // max over |x| >= 0
   else if constexpr (RED == 3) return INFINITY;
   else return 0.0;
 }
 
-// The fixed tail of every deterministic reduction: 64-lane __shfl_down per
-// wave -> one LDS slot per wave -> thread 0 combines the BLK/64 slots in
-// order.  The result is valid in thread 0 only.  All calls in one kernel
-// share the LDS slots: a second call needs a __syncthreads() before it.
+// 64-lane __shfl_down tree of one wave; the result is valid in lane 0
 template <int RED>
-__device__ __forceinline__ double block_reduce(double acc) {
+__device__ __forceinline__ double wave_reduce(double acc) {
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1)
     acc = red_combine<RED>(acc, __shfl_down(acc, off, 64));
+  return acc;
+}
+
+// The fixed tail of every deterministic reduction: wave_reduce -> one LDS
+// slot per wave -> thread 0 combines the BLK/64 slots in order.  The result
+// is valid in thread 0 only.  All calls in one kernel share the LDS slots:
+// a second call needs a __syncthreads() before it.
+template <int RED>
+__device__ __forceinline__ double block_reduce(double acc) {
+  acc = wave_reduce<RED>(acc);
   __shared__ double lds[BLK / 64];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   if (lane == 0) lds[wave] = acc;
@@ -706,36 +650,64 @@ __global__ void __launch_bounds__(BLK) reduce_stage1(
   if (threadIdx.x == 0) partials[blockIdx.x] = r;
 }
 
-template <int RED>
+// One block combines the np stage-1 partials of each of LANES result lanes
+// (lane l's partials start at partials + l * NPARTIAL) into out[l].  np == 0
+// leaves red_init<RED>(): the empty result.
+template <int RED, int LANES>
 __global__ void __launch_bounds__(BLK) reduce_stage2(
     const double* __restrict__ partials, int64_t np, double* __restrict__ out) {
-  double acc = red_init<RED>();
-  for (int64_t i = threadIdx.x; i < np; i += BLK)
-    acc = red_combine<RED>(acc, partials[i]);
-  const double r = block_reduce<RED>(acc);
-  if (threadIdx.x == 0) *out = r;
+  double acc[LANES], r[LANES];
+#pragma unroll
+  for (int l = 0; l < LANES; ++l) acc[l] = red_init<RED>();
+  for (int64_t i = threadIdx.x; i < np; i += BLK) {
+#pragma unroll
+    for (int l = 0; l < LANES; ++l)
+      acc[l] = red_combine<RED>(acc[l], partials[l * NPARTIAL + i]);
+  }
+#pragma unroll
+  for (int l = 0; l < LANES; ++l) {
+    if (l > 0) __syncthreads();
+    r[l] = block_reduce<RED>(acc[l]);
+  }
+  if (threadIdx.x == 0) {
+#pragma unroll
+    for (int l = 0; l < LANES; ++l) out[l] = r[l];
+  }
 }
 
-template <typename T, int RED, bool CPLX = false>
-static int reduce_launch(void* stream, const void* x, const void* y, int64_t n,
-                         double p, void* ws, void* out) {
-  if (n < 0 || !ws || !out) return PAM_EARG;
+// The one two-stage deterministic reduction.  stage1(grid, s) launches the
+// family's stage-1 kernel on min(ceil(n / BLK), NPARTIAL) blocks, each
+// writing one partial per result lane into ws; stage 2 combines them into
+// out[0..LANES).  n == 0 launches stage 2 alone, which writes the empty
+// result: no array is read and nothing blocks the host.  The caller has
+// checked its arguments.
+template <int RED, int LANES, typename F>
+static int reduce_launch(void* stream, int64_t n, void* ws, void* out,
+                         F&& stage1) {
   hipStream_t s = (hipStream_t)stream;
-  if (n == 0) {  // x, y are not read: an empty block's pointer is NULL
-    double z = (RED == 3) ? INFINITY : 0.0;
-    // degenerate case: blocking copy (no stack-lifetime hazard)
-    return check(hipMemcpy(out, &z, sizeof(double), hipMemcpyHostToDevice));
-  }
-  if (!x || (RED == 0 && !y)) return PAM_EARG;
   int64_t nb = (n + BLK - 1) / BLK;
   if (nb > NPARTIAL) nb = NPARTIAL;
-  hipLaunchKernelGGL((reduce_stage1<T, RED, CPLX>), dim3(nb), dim3(BLK), 0, s,
-                     (const T*)x, (const T*)y, n, p, (double*)ws);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return (int)e;
-  hipLaunchKernelGGL((reduce_stage2<RED>), dim3(1), dim3(BLK), 0, s,
+  if (nb > 0) {
+    stage1(dim3((uint32_t)nb), s);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return (int)e;
+  }
+  hipLaunchKernelGGL((reduce_stage2<RED, LANES>), dim3(1), dim3(BLK), 0, s,
                      (const double*)ws, nb, (double*)out);
   return check(hipGetLastError());
+}
+
+// dot and the norms; x (and y of the dot) may be NULL when n == 0
+template <typename T, int RED, bool CPLX>
+static int norm_launch(void* stream, const void* x, const void* y, int64_t n,
+                       double p, void* ws, void* out) {
+  if (n < 0 || !ws || !out) return PAM_EARG;
+  if (n > 0 && (!x || (RED == 0 && !y))) return PAM_EARG;
+  return reduce_launch<RED, 1>(stream, n, ws, out, [&](dim3 grid,
+                                                       hipStream_t s) {
+    hipLaunchKernelGGL((reduce_stage1<T, RED, CPLX>), grid, dim3(BLK), 0, s,
+                       (const T*)x, (const T*)y, n, p, (double*)ws);
+  });
 }
 
 // ---- complex dot (out = sum x*y or sum conj(x)*y; 2-double result)
@@ -762,92 +734,41 @@ __global__ void __launch_bounds__(BLK) cdot_stage1(
   }
 }
 
-__global__ void __launch_bounds__(BLK) cdot_stage2(
-    const double* __restrict__ pre, const double* __restrict__ pim,
-    int64_t np, double* __restrict__ out) {
-  double ar = 0.0, ai = 0.0;
-  for (int64_t i = threadIdx.x; i < np; i += BLK) {
-    ar += pre[i];
-    ai += pim[i];
-  }
-  const double sr = block_reduce<0>(ar);
-  __syncthreads();
-  const double si = block_reduce<0>(ai);
-  if (threadIdx.x == 0) {
-    out[0] = sr;
-    out[1] = si;
-  }
-}
-
-template <typename T>
-static int cdot_launch(void* stream, const void* x, const void* y, int64_t n,
-                       int conjx, void* ws, void* out) {
-  if (n < 0 || !ws || !out) return PAM_EARG;
-  hipStream_t s = (hipStream_t)stream;
-  if (n == 0) {  // x, y are not read: an empty block's pointer is NULL
-    double z[2] = {0.0, 0.0};
-    return check(hipMemcpy(out, z, sizeof(z), hipMemcpyHostToDevice));
-  }
-  if (!x || !y) return PAM_EARG;
-  int64_t nb = (n + BLK - 1) / BLK;
-  if (nb > NPARTIAL) nb = NPARTIAL;
-  double* pre = (double*)ws;
-  double* pim = pre + NPARTIAL;
-  if (conjx)
-    hipLaunchKernelGGL((cdot_stage1<T, true>), dim3(nb), dim3(BLK), 0, s,
-                       (const T*)x, (const T*)y, n, pre, pim);
-  else
-    hipLaunchKernelGGL((cdot_stage1<T, false>), dim3(nb), dim3(BLK), 0, s,
-                       (const T*)x, (const T*)y, n, pre, pim);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return (int)e;
-  hipLaunchKernelGGL(cdot_stage2, dim3(1), dim3(BLK), 0, s, pre, pim, nb,
-                     (double*)out);
-  return check(hipGetLastError());
-}
-
 extern "C" int pam_cdot(void* stream, const void* x, const void* y, int64_t n,
                         int conjx, void* ws, void* out, int dtype) {
-  if (dtype == PAM_C128)
-    return cdot_launch<double>(stream, x, y, n, conjx, ws, out);
-  if (dtype == PAM_C64)
-    return cdot_launch<float>(stream, x, y, n, conjx, ws, out);
-  return PAM_EDTYPE;
+  return with_cplx(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    if (n < 0 || !ws || !out) return PAM_EARG;
+    if (n > 0 && (!x || !y)) return PAM_EARG;
+    double* pre = (double*)ws;  // re partials; im partials NPARTIAL further
+    return reduce_launch<0, 2>(stream, n, ws, out, [&](dim3 grid,
+                                                       hipStream_t s) {
+      with_bool(conjx != 0, [&](auto cj) {
+        hipLaunchKernelGGL((cdot_stage1<T, decltype(cj)::value>), grid,
+                           dim3(BLK), 0, s, (const T*)x, (const T*)y, n, pre,
+                           pre + NPARTIAL);
+      });
+    });
+  });
 }
 
 extern "C" int pam_dot(void* stream, const void* x, const void* y, int64_t n,
                        void* ws, void* out, int dtype) {
-  if (dtype == PAM_F64)
-    return reduce_launch<double, 0>(stream, x, y, n, 0.0, ws, out);
-  if (dtype == PAM_F32)
-    return reduce_launch<float, 0>(stream, x, y, n, 0.0, ws, out);
-  return PAM_EDTYPE;
+  return with_real(dtype, [&](auto t) {
+    using T = typename decltype(t)::type;
+    return norm_launch<T, 0, false>(stream, x, y, n, 0.0, ws, out);
+  });
 }
 
 extern "C" int pam_norm_local(void* stream, const void* x, int64_t n, int op,
                               double p, void* ws, void* out, int dtype) {
-  if (op < 0 || op > 3) return PAM_EOP;
-#define NORM_CASE(T)                                                          \
-  switch (op) {                                                               \
-    case 0: return reduce_launch<T, 1>(stream, x, nullptr, n, p, ws, out);    \
-    case 1: return reduce_launch<T, 2>(stream, x, nullptr, n, p, ws, out);    \
-    case 2: return reduce_launch<T, 3>(stream, x, nullptr, n, p, ws, out);    \
-    default: return reduce_launch<T, 4>(stream, x, nullptr, n, p, ws, out);   \
-  }
-  if (dtype == PAM_F64) { NORM_CASE(double) }
-  if (dtype == PAM_F32) { NORM_CASE(float) }
-#undef NORM_CASE
-#define CNORM_CASE(T)                                                         \
-  switch (op) {                                                               \
-    case 0: return reduce_launch<T, 1, true>(stream, x, nullptr, n, p, ws, out); \
-    case 1: return reduce_launch<T, 2, true>(stream, x, nullptr, n, p, ws, out); \
-    case 2: return reduce_launch<T, 3, true>(stream, x, nullptr, n, p, ws, out); \
-    default: return reduce_launch<T, 4, true>(stream, x, nullptr, n, p, ws, out); \
-  }
-  if (dtype == PAM_C128) { CNORM_CASE(double) }
-  if (dtype == PAM_C64) { CNORM_CASE(float) }
-#undef CNORM_CASE
-  return PAM_EDTYPE;
+  return with_int<0, 3>(op, PAM_EOP, [&](auto o) {  // RED = op + 1
+    return with_dtype(dtype, [&](auto t, auto cplx) {
+      using T = typename decltype(t)::type;
+      return norm_launch<T, decltype(o)::value + 1, decltype(cplx)::value>(
+          stream, x, nullptr, n, p, ws, out);
+    });
+  });
 }
 
 // ---------------------------------------------------------------------------
@@ -955,6 +876,7 @@ __global__ void __launch_bounds__(BLK) group_shrink_kernel(
   }
 }
 
+// the arguments are checked and n > 0; b is all NULL (no shift) or all set
 template <typename T, bool CPLX, int NC>
 static int group_shrink_launch(void* stream, int mode, void* const* y,
                                const void* const* a, const void* const* b,
@@ -970,36 +892,17 @@ static int group_shrink_launch(void* stream, int mode, void* const* y,
               ((uintptr_t)a[c] % 16 == 0) &&
               (!shift || (uintptr_t)b[c] % 16 == 0);
   }
-  constexpr int E = CPLX ? 2 : 1;
-  constexpr int V = VecW<T>::value;
-  hipStream_t s = (hipStream_t)stream;
-  const int64_t grid = grid_1d(aligned ? (n * E) / V + 1 : n);
-#define GROUP_GO(SHIFT, VEC)                                                  \
-  hipLaunchKernelGGL((group_shrink_kernel<T, NC, CPLX, SHIFT, VEC>),          \
-                     dim3(grid), dim3(BLK), 0, s, P, (T)beta, (T)thresh,      \
-                     mode, n)
-  if (shift) {
-    if (aligned) GROUP_GO(true, true);
-    else GROUP_GO(true, false);
-  } else {
-    if (aligned) GROUP_GO(false, true);
-    else GROUP_GO(false, false);
-  }
-#undef GROUP_GO
-  return check(hipGetLastError());
-}
-
-template <typename T, bool CPLX>
-static int group_shrink_nc(void* stream, int mode, int64_t ncomp,
-                           void* const* y, const void* const* a,
-                           const void* const* b, double beta, int64_t n,
-                           double thresh) {
-  switch (ncomp) {
-    case 1: return group_shrink_launch<T, CPLX, 1>(stream, mode, y, a, b, beta, n, thresh);
-    case 2: return group_shrink_launch<T, CPLX, 2>(stream, mode, y, a, b, beta, n, thresh);
-    case 3: return group_shrink_launch<T, CPLX, 3>(stream, mode, y, a, b, beta, n, thresh);
-    default: return group_shrink_launch<T, CPLX, 4>(stream, mode, y, a, b, beta, n, thresh);
-  }
+  return vec_launch<T>(aligned, {}, [&](auto v) {
+    constexpr int E = CPLX ? 2 : 1;
+    constexpr bool VEC = decltype(v)::value > 1;
+    const int64_t grid = grid_1d(VEC ? (n * E) / decltype(v)::value + 1 : n);
+    with_bool(shift, [&](auto sh) {
+      hipLaunchKernelGGL(
+          (group_shrink_kernel<T, NC, CPLX, decltype(sh)::value, VEC>),
+          dim3((uint32_t)grid), dim3(BLK), 0, (hipStream_t)stream, P, (T)beta,
+          (T)thresh, mode, n);
+    });
+  });
 }
 
 extern "C" int pam_group_shrink(void* stream, int mode, int64_t ncomp,
@@ -1020,14 +923,15 @@ extern "C" int pam_group_shrink(void* stream, int mode, int64_t ncomp,
   }
   if (n < 0 || !(thresh >= 0.0)) return PAM_EARG;
   if (mode != 0 && mode != 1) return PAM_EOP;
-  if (dtype < PAM_F64 || dtype > PAM_C64) return PAM_EDTYPE;
-  if (n == 0) return 0;
-  switch (dtype) {
-    case PAM_F64: return group_shrink_nc<double, false>(stream, mode, ncomp, y, a, b, beta, n, thresh);
-    case PAM_F32: return group_shrink_nc<float, false>(stream, mode, ncomp, y, a, b, beta, n, thresh);
-    case PAM_C128: return group_shrink_nc<double, true>(stream, mode, ncomp, y, a, b, beta, n, thresh);
-    default: return group_shrink_nc<float, true>(stream, mode, ncomp, y, a, b, beta, n, thresh);
-  }
+  return with_dtype(dtype, [&](auto t, auto cplx) {
+    using T = typename decltype(t)::type;
+    constexpr bool CPLX = decltype(cplx)::value;
+    if (n == 0) return 0;
+    return with_int<1, PAM_GROUP_MAX>(ncomp, PAM_EARG, [&](auto nc) {
+      return group_shrink_launch<T, CPLX, decltype(nc)::value>(
+          stream, mode, y, a, b, beta, n, thresh);
+    });
+  });
 }
 
 // out = sum_i sqrt(sum_c |x_c[i]|^2) in float64: stage 1 is pam_dot's fixed
@@ -1063,34 +967,6 @@ __global__ void __launch_bounds__(BLK) group_norm_stage1(
   if (threadIdx.x == 0) partials[blockIdx.x] = r;
 }
 
-template <typename T, bool CPLX, int NC>
-static int group_norm_launch(void* stream, const void* const* x, int64_t n,
-                             void* ws, void* out) {
-  GroupIn<T, NC> P;
-  for (int c = 0; c < NC; ++c) P.x[c] = (const T*)x[c];
-  hipStream_t s = (hipStream_t)stream;
-  int64_t nb = (n + BLK - 1) / BLK;
-  if (nb > NPARTIAL) nb = NPARTIAL;
-  hipLaunchKernelGGL((group_norm_stage1<T, NC, CPLX>), dim3(nb), dim3(BLK), 0,
-                     s, P, n, (double*)ws);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return (int)e;
-  hipLaunchKernelGGL((reduce_stage2<0>), dim3(1), dim3(BLK), 0, s,
-                     (const double*)ws, nb, (double*)out);
-  return check(hipGetLastError());
-}
-
-template <typename T, bool CPLX>
-static int group_norm_nc(void* stream, int64_t ncomp, const void* const* x,
-                         int64_t n, void* ws, void* out) {
-  switch (ncomp) {
-    case 1: return group_norm_launch<T, CPLX, 1>(stream, x, n, ws, out);
-    case 2: return group_norm_launch<T, CPLX, 2>(stream, x, n, ws, out);
-    case 3: return group_norm_launch<T, CPLX, 3>(stream, x, n, ws, out);
-    default: return group_norm_launch<T, CPLX, 4>(stream, x, n, ws, out);
-  }
-}
-
 extern "C" int pam_group_norm(void* stream, int64_t ncomp, const void* x0,
                               const void* x1, const void* x2, const void* x3,
                               int64_t n, void* ws, void* out, int dtype) {
@@ -1099,15 +975,20 @@ extern "C" int pam_group_norm(void* stream, int64_t ncomp, const void* x0,
   for (int64_t c = 0; c < ncomp; ++c)
     if (!x[c]) return PAM_EARG;
   if (n < 0 || !ws || !out) return PAM_EARG;
-  if (dtype < PAM_F64 || dtype > PAM_C64) return PAM_EDTYPE;
-  if (n == 0)  // no launch; stream-ordered, so graph capture stays legal
-    return check(hipMemsetAsync(out, 0, sizeof(double), (hipStream_t)stream));
-  switch (dtype) {
-    case PAM_F64: return group_norm_nc<double, false>(stream, ncomp, x, n, ws, out);
-    case PAM_F32: return group_norm_nc<float, false>(stream, ncomp, x, n, ws, out);
-    case PAM_C128: return group_norm_nc<double, true>(stream, ncomp, x, n, ws, out);
-    default: return group_norm_nc<float, true>(stream, ncomp, x, n, ws, out);
-  }
+  return with_dtype(dtype, [&](auto t, auto cplx) {
+    using T = typename decltype(t)::type;
+    constexpr bool CPLX = decltype(cplx)::value;
+    return with_int<1, PAM_GROUP_MAX>(ncomp, PAM_EARG, [&](auto nc) {
+      constexpr int NC = decltype(nc)::value;
+      GroupIn<T, NC> P;
+      for (int c = 0; c < NC; ++c) P.x[c] = (const T*)x[c];
+      return reduce_launch<0, 1>(stream, n, ws, out, [&](dim3 grid,
+                                                         hipStream_t s) {
+        hipLaunchKernelGGL((group_norm_stage1<T, NC, CPLX>), grid, dim3(BLK),
+                           0, s, P, n, (double*)ws);
+      });
+    });
+  });
 }
 
 // ---------------------------------------------------------------------------
@@ -1145,8 +1026,7 @@ __global__ void __launch_bounds__(BLK) gemv_n_kernel(
     }
     for (int64_t c = ncv * V + lane; c < nc; c += 64)
       acc += (double)row[c] * (double)x[c];
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) acc += __shfl_down(acc, off, 64);
+    acc = wave_reduce<0>(acc);
     if (lane == 0) y[r] = (T)acc;
   }
 }
@@ -1190,38 +1070,30 @@ __global__ void __launch_bounds__(BLK) gemv_t_stage2(
   y[c] = (T)acc;
 }
 
+// the vector kernels also need whole rows of vectors: nc % VecW<T> == 0
 template <typename T>
 static int gemv_launch(void* stream, int trans, const void* A, const void* x,
                        void* y, int64_t nr, int64_t nc, void* ws) {
   if (nr <= 0 || nc <= 0 || !A || !x || !y) return PAM_EARG;
   hipStream_t s = (hipStream_t)stream;
+  const bool rows_ok = nc % VecW<T>::value == 0;
   if (!trans) {
-    constexpr int V = VecW<T>::value;
-    const bool vec_ok = (nc % V == 0) && ((uintptr_t)A % 16 == 0) &&
-                        ((uintptr_t)x % 16 == 0);
     int64_t nb = (nr + (BLK / 64) - 1) / (BLK / 64);
     if (nb > 4096) nb = 4096;
-    if (vec_ok)
-      hipLaunchKernelGGL((gemv_n_kernel<T, V>), dim3((uint32_t)nb), dim3(BLK),
-                         0, s, (const T*)A, (const T*)x, (T*)y, nr, nc);
-    else
-      hipLaunchKernelGGL((gemv_n_kernel<T, 1>), dim3((uint32_t)nb), dim3(BLK),
-                         0, s, (const T*)A, (const T*)x, (T*)y, nr, nc);
-    return check(hipGetLastError());
+    return vec_launch<T>(rows_ok, {A, x}, [&](auto v) {
+      hipLaunchKernelGGL((gemv_n_kernel<T, decltype(v)::value>),
+                         dim3((uint32_t)nb), dim3(BLK), 0, s, (const T*)A,
+                         (const T*)x, (T*)y, nr, nc);
+    });
   }
   if (!ws) return PAM_EARG;
-  constexpr int V = VecW<T>::value;
-  const bool vec_ok = (nc % V == 0) && ((uintptr_t)A % 16 == 0);
-  const int64_t ncl = vec_ok ? nc / V : nc;
-  dim3 g1((uint32_t)((ncl + BLK - 1) / BLK), GEMV_CHUNKS);
-  if (vec_ok)
+  const int rc = vec_launch<T>(rows_ok, {A}, [&](auto v) {
+    constexpr int V = decltype(v)::value;
+    dim3 g1((uint32_t)((nc / V + BLK - 1) / BLK), GEMV_CHUNKS);
     hipLaunchKernelGGL((gemv_t_stage1<T, V>), g1, dim3(BLK), 0, s,
                        (const T*)A, (const T*)x, (double*)ws, nr, nc);
-  else
-    hipLaunchKernelGGL((gemv_t_stage1<T, 1>), g1, dim3(BLK), 0, s,
-                       (const T*)A, (const T*)x, (double*)ws, nr, nc);
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return (int)e;
+  });
+  if (rc != 0) return rc;
   hipLaunchKernelGGL((gemv_t_stage2<T>),
                      dim3((uint32_t)((nc + BLK - 1) / BLK)), dim3(BLK), 0, s,
                      (const double*)ws, (T*)y, nc);
@@ -1230,11 +1102,10 @@ static int gemv_launch(void* stream, int trans, const void* A, const void* x,
 
 extern "C" int pam_gemv(void* stream, int trans, const void* A, const void* x,
                         void* y, int64_t nr, int64_t nc, void* ws, int dtype) {
-  if (dtype == PAM_F64)
-    return gemv_launch<double>(stream, trans, A, x, y, nr, nc, ws);
-  if (dtype == PAM_F32)
-    return gemv_launch<float>(stream, trans, A, x, y, nr, nc, ws);
-  return PAM_EDTYPE;
+  return with_real(dtype, [&](auto t) {
+    return gemv_launch<typename decltype(t)::type>(stream, trans, A, x, y, nr,
+                                                   nc, ws);
+  });
 }
 
 // ---------------------------------------------------------------------------
@@ -1467,11 +1338,6 @@ __global__ void __launch_bounds__(BLK) fd_roll_kernel(
 
 // ---- launch plan: which kernel, which lane width, which grid -------------
 
-static int64_t fd_env(const char* name, int64_t dflt) {
-  const char* e = getenv(name);
-  return e ? atoll(e) : dflt;
-}
-
 enum { FD_ROW = 0, FD_ROLL = 1, FD_BAND = 2 };  // pam_fd_variant's codes
 
 struct FdPlan {
@@ -1492,12 +1358,12 @@ struct FdPlan {
 // Every kernel but the V = 1 row-parallel one needs 16-B lanes: 16-B
 // aligned pointers and m a multiple of 16 / tsize.
 static FdPlan fd_plan(int tsize, int64_t m, int64_t nrows, bool align16) {
-  static const int64_t rollov = fd_env("PAM_FD_ROLL", 0);
-  static const int64_t longrow = fd_env("PAM_FD_LONGROW", 4 << 20);
-  static const int64_t gycap = fd_env("PAM_FD_GY", 65535);
-  static const int64_t totcap = fd_env("PAM_FD_CAP", 262144);
-  static const int64_t rolltgt = fd_env("PAM_FD_ROLL_TGT", 2048);
-  const int64_t bandov = fd_env("PAM_FD_BAND", 0);
+  static const int64_t rollov = env_int("PAM_FD_ROLL", 0);
+  static const int64_t longrow = env_int("PAM_FD_LONGROW", 4 << 20);
+  static const int64_t gycap = env_int("PAM_FD_GY", 65535);
+  static const int64_t totcap = env_int("PAM_FD_CAP", 262144);
+  static const int64_t rolltgt = env_int("PAM_FD_ROLL_TGT", 2048);
+  const int64_t bandov = env_int("PAM_FD_BAND", 0);
   const int vw = 16 / tsize;
   const bool lanes16 = align16 && m % vw == 0;
   const int64_t rowbytes = m * (int64_t)tsize;

@@ -1,5 +1,9 @@
-"""Kernel perf probe (run on the GPU box): GEMM TF/s, GEMV GB/s, stencil
-variants.  Prints one JSON line per measurement."""
+"""Kernel perf probe (run on the GPU box): GEMM TF/s, GEMV GB/s and the
+vector primitives (HBM-bound rows in TB/s by the algorithmic byte count,
+launch-bound rows in host microseconds per call).  Prints one JSON line per
+measurement.  --rows picks the families, --lib another build's libpam.so
+(for A/Bs against this tree's)."""
+import argparse
 import json
 import os
 import sys
@@ -63,8 +67,105 @@ def bench_gemv(n, label):
                           "ms": sec * 1e3, "GB/s": gbs}), flush=True)
 
 
+NBENCH = 2048 * 2048 * 128      # the bench length (scripts/gpu_ew_sweep.py)
+
+
+def rand(n, tdt=torch.float64):
+    return torch.rand(n, dtype=tdt, device="cuda") * 2 - 1
+
+
+def bench_prim(label, nbytes, call, iters=20):
+    """One HBM-bound row: call() launches, nbytes is what it must move."""
+    def run():
+        _ffi.checked(call(), label)
+    sec = timeit(run, iters=iters)
+    print(json.dumps({"probe": label, "ms": sec * 1e3,
+                      "TB/s": nbytes / sec / 1e12}), flush=True)
+
+
+def bench_launch(label, call, calls=1000):
+    """One launch-bound row: host time per call, the queue drained after."""
+    for _ in range(50):
+        call()
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(calls):
+        call()
+    sec = (time.perf_counter() - t0) / calls
+    torch.cuda.synchronize()
+    print(json.dumps({"probe": label, "calls": calls,
+                      "host_us": sec * 1e6}), flush=True)
+
+
+def bench_primitives():
+    lib = _ffi.lib()
+    s = torch.cuda.current_stream().cuda_stream
+    n = NBENCH
+    ws = torch.empty(2 * int(lib.pam_reduce_ws_elems()), dtype=torch.float64,
+                     device="cuda")
+    out = torch.empty(2, dtype=torch.float64, device="cuda")
+    alpha = torch.full((1,), 0.5, dtype=torch.float64, device="cuda")
+    w, o = ws.data_ptr(), out.data_ptr()
+
+    # float64 at the bench length
+    x, y, z = rand(n), rand(n), torch.empty(n, dtype=torch.float64,
+                                            device="cuda")
+    xp, yp, zp = x.data_ptr(), y.data_ptr(), z.data_ptr()
+    bench_prim("axpy_f64", 24 * n, lambda: lib.pam_axpy(s, yp, xp, 0.5, n, 0))
+    bench_prim("axpy_d_f64", 24 * n, lambda: lib.pam_axpy_d(
+        s, yp, xp, alpha.data_ptr(), 1.0, n, 0))
+    bench_prim("add_f64", 24 * n, lambda: lib.pam_add(s, zp, xp, yp, n, 0))
+    bench_prim("thresh_soft_f64", 16 * n,
+               lambda: lib.pam_thresh(s, zp, xp, n, 0, 0.3, 0))
+    bench_prim("dot_f64", 16 * n, lambda: lib.pam_dot(s, xp, yp, n, w, o, 0))
+    bench_prim("norm2_f64", 8 * n,
+               lambda: lib.pam_norm_local(s, xp, n, 0, 2.0, w, o, 0))
+    # the same storage as n complex64 (8 B each)
+    x32, y32, z32 = (t.view(torch.float32) for t in (x, y, z))
+    x32.copy_(rand(2 * n, torch.float32))
+    y32.copy_(rand(2 * n, torch.float32))
+    bench_prim("cmul_c64", 24 * n, lambda: lib.pam_cmul(s, zp, xp, yp, n, 3))
+    bench_prim("cdot_c64", 16 * n,
+               lambda: lib.pam_cdot(s, xp, yp, n, 1, w, o, 3))
+    del x32, y32, z32
+    x.copy_(rand(n))
+    y.copy_(rand(n))
+    # ... as 2 float64 components of n / 2: y_c = shrink(a_c + beta b_c)
+    h = n // 2
+    hb = 8 * h
+    bench_prim("group_shrink_nc2_shift_f64", 24 * n,
+               lambda: lib.pam_group_shrink(
+                   s, 0, 2, zp, zp + hb, None, None, xp, xp + hb, None, None,
+                   yp, yp + hb, None, None, -0.5, h, 0.3, 0))
+    bench_prim("group_norm_nc2_f64", 8 * n, lambda: lib.pam_group_norm(
+        s, 2, xp, xp + hb, None, None, h, w, o, 0))
+    # ... as n / 2 complex128: 16 B read + 8 B written per element
+    bench_prim("unzip_c128", 12 * n, lambda: lib.pam_unzip(s, zp, xp, h, 2))
+    nt = 2048
+    bench_prim("zip_t_c128", 12 * n,
+               lambda: lib.pam_zip_t(s, zp, xp, nt, h // nt, 2))
+    del x, y, z
+
+    m = 4096
+    xs, ys = rand(m), rand(m)
+    bench_launch("axpy_f64_n4096", lambda: lib.pam_axpy(
+        s, ys.data_ptr(), xs.data_ptr(), 0.5, m, 0))
+    bench_launch("dot_f64_n4096", lambda: lib.pam_dot(
+        s, xs.data_ptr(), ys.data_ptr(), m, w, o, 0))
+
+
 def main():
+    ap = argparse.ArgumentParser(description=__doc__.split(".")[0])
+    ap.add_argument("--rows", choices=("all", "gemm", "prim"), default="all")
+    ap.add_argument("--lib", help="libpam.so to load instead of the tree's")
+    args = ap.parse_args()
+    if args.lib:
+        _ffi._LIB_PATH = os.path.abspath(args.lib)
     init_default_comm(torch.device("cuda:0"))
+    if args.rows != "gemm":
+        bench_primitives()
+    if args.rows == "prim":
+        return
     bench_gemm(4096, 4096, 4096, torch.float32, "gemm_f32")
     bench_gemm(8192, 8192, 8192, torch.float32, "gemm_f32")
     bench_gemm(4096, 4096, 4096, torch.float64, "gemm_f64")

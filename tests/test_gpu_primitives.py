@@ -6,7 +6,7 @@ tests/primref.py (itself checked in tests/test_primref_cpu.py).
 Every operand is a view into a larger, sentinel-filled buffer
 (primref.Placed): 16-byte aligned or one element off it, which selects the
 vector or the scalar (V=1) kernel, and each operand is misaligned on its
-own because the launchers AND the alignment of all pointers.  After a
+own because vec_launch ANDs the alignment of all pointers.  After a
 launch the guards of the output must hold the sentinel bit for bit and the
 inputs their uploaded bits.  Calls go through pylops_mpi_amd.kernels; only
 a complex128 operand one REAL off alignment, which torch cannot express,
@@ -536,6 +536,44 @@ def test_reductions_nonfinite(dname):
                 assert norm(x, 0, 2.0) == np.inf, msg
                 poke(x, pos, x0[pos])
             assert x.untouched() and y.untouched()
+
+
+@pytest.mark.parametrize("dname", NAMES)
+def test_empty_reductions_on_side_stream(dname):
+    """n == 0 on a non-default stream: ``out`` is filled with the sentinel
+    on that stream, then every reduction is called there with NULL arrays.
+    After a stream sync ``out`` holds the documented empty result
+    (include/pam.h) and the slots past it the sentinel: the result is
+    written in stream order, after the fill.  pam_group_norm returns
+    PAM_EARG for a NULL among its first ncomp components whatever n is
+    (tests/test_group_cpu.py), so its unread components point at ``ws``."""
+    lib, code = _ffi.lib(), NAMES.index(dname)
+    side = torch.cuda.Stream()
+    ws = torch.empty(2 * int(lib.pam_reduce_ws_elems()), dtype=torch.float64,
+                     device="cuda:0")
+    out = torch.empty(4, dtype=torch.float64, device="cuda:0")
+    side.wait_stream(torch.cuda.current_stream())
+    s, w, o = side.cuda_stream, ws.data_ptr(), out.data_ptr()
+    calls = [(f"norm_local op {op}", [want], lambda op=op: lib.pam_norm_local(
+        s, None, 0, op, 2.0, w, o, code))
+        for op, want in enumerate((0.0, 0.0, np.inf, 0.0))]
+    if pr.is_complex(DT[dname]):
+        calls += [(f"cdot conjx={c}", [0.0, 0.0], lambda c=c: lib.pam_cdot(
+            s, None, None, 0, c, w, o, code)) for c in (0, 1)]
+    else:
+        calls.append(("dot", [0.0], lambda: lib.pam_dot(
+            s, None, None, 0, w, o, code)))
+    calls += [(f"group_norm ncomp={k}", [0.0], lambda k=k: lib.pam_group_norm(
+        s, k, *([w] * k + [None] * (4 - k)), 0, w, o, code))
+        for k in (1, 4)]
+    for name, want, call in calls:
+        with torch.cuda.stream(side):
+            out.fill_(pr.SENTINEL)
+        assert call() == 0, (dname, name)
+        side.synchronize()
+        got = out.cpu().numpy()
+        assert pr.bits(got).tolist() == pr.bits(np.array(
+            want + [pr.SENTINEL] * (4 - len(want)))).tolist(), (dname, name)
 
 
 # --------------------------------------------------------------------- GEMV
