@@ -216,6 +216,31 @@ int pam_group_norm(void* stream, int64_t ncomp,
  *   8 fd2 forward  matvec   9 fd2 forward  rmatvec
  *  10 fd2 backward matvec  11 fd2 backward rmatvec
  *  12 fd2 centered matvec  13 fd2 centered rmatvec
+ *
+ * Arithmetic, per output, in the block's type T: acc = 0; for each term of
+ * the op that is active on global row g, acc += T(c_t) * x[g + off_t] (the
+ * product rounded, then the sum); with edge the fix-up of the row; last
+ * acc *= T(coeff).  All three kernels and pam_fd_serial share it bit for
+ * bit.
+ *
+ * Shortest axis.  With edge != 0 the fix-ups of the centered ops read rows
+ * next to either end of the axis, which must exist:
+ *   ops 4, 5          nglob >= 2   (rows 1 and N-2)
+ *   ops 6, 7, 12, 13  nglob >= 3   (rows 2 and N-3)
+ *   every other op, and edge == 0: nglob >= 1
+ * pam_fd_apply (nglob) and pam_fd_serial (d) return PAM_EARG on a shorter
+ * axis, before anything is launched; the reference raises IndexError there.
+ *
+ * Ops 6/7 at N == 3 with edge: op 7 is NOT the transpose of op 6.  The
+ * matvec overwrites row 1 twice (y[1] and y[-2] are one row), the rmatvec
+ * adds both fix-ups: its matrix is [[-1,-1,0],[1,0,-1],[0,1,1]] where the
+ * transpose has -0.5 at [0,1] and 0.5 at [2,1].  This is the reference's
+ * own slice algebra, kept for parity; every other (op, edge, N) pair is an
+ * exact transpose pair.
+ *
+ * PAM_EOP: op outside 0..13; PAM_EDTYPE: dtype not PAM_F64 / PAM_F32 (a
+ * complex block runs as its real view, m doubled); PAM_EARG: nloc < 0,
+ * m <= 0, rbegin < 0, rend > nloc, or the axis too short.
  * ------------------------------------------------------------------ */
 int64_t pam_fd_halo_width(int op);
 /* rbegin/rend restrict the computed LOCAL row range [rbegin, rend) so the

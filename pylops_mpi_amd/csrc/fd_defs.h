@@ -174,6 +174,19 @@ static inline int fd_dispatch_op(int op, F&& f) {
   return with_int<0, FD_NOPS - 1>(op, PAM_EOP, f);
 }
 
+// Shortest axis the stencil is defined on.  The edge fix-ups of the
+// centered ops read one (ops 4/5) or two (6/7, 12/13) rows away from either
+// end of the axis; on a shorter axis those rows do not exist, and the entry
+// points answer PAM_EARG before anything is launched (include/pam.h).
+static inline int64_t fd_min_rows(int op, int edge) {
+  if (!edge) return 1;
+  switch (op) {
+    case 4: case 5: return 2;
+    case 6: case 7: case 12: case 13: return 3;
+    default: return 1;
+  }
+}
+
 
 template <typename T>
 struct Rows {

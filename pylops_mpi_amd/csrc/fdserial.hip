@@ -92,6 +92,7 @@ static int fd_serial_launch(void* stream, int edge, const void* x, void* y,
                             int64_t batch, int64_t d, int64_t m,
                             double coeff) {
   if (batch <= 0 || d <= 0 || m <= 0) return PAM_EARG;
+  if (d < fd_min_rows(OP, edge)) return PAM_EARG;
   hipStream_t s = (hipStream_t)stream;
   hipLaunchKernelGGL((fd_serial_kernel<T, OP>),
                      dim3(grid_1d_s(batch * d * m)), dim3(BLK), 0, s,

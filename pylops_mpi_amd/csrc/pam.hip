@@ -1473,6 +1473,7 @@ static int fd_launch(void* stream, int edge, const void* x, const void* gf,
                      int64_t row0, int64_t nglob, int64_t rbegin,
                      int64_t rend, double coeff) {
   if (nloc < 0 || m <= 0 || rbegin < 0 || rend > nloc) return PAM_EARG;
+  if (nglob < fd_min_rows(OP, edge)) return PAM_EARG;
   const int64_t nrows = rend - rbegin;
   if (nloc == 0 || nrows <= 0) return 0;
   const bool align16 = ((uintptr_t)x % 16 == 0) && ((uintptr_t)y % 16 == 0) &&

@@ -414,6 +414,21 @@ def fd_halo_width(op: int) -> int:  # neighbour planes read per side
     return int(_ffi.lib().pam_fd_halo_width(int(op)))
 
 
+# shortest axis on which the edge fix-ups of an op are defined (include/pam.h,
+# the table next to the op codes); every other op, and edge False: 1
+_FD_EDGE_MIN = {4: 2, 5: 2, 6: 3, 7: 3, 12: 3, 13: 3}
+
+
+def fd_min_rows(op: int, edge: bool) -> int:
+    return _FD_EDGE_MIN.get(int(op), 1) if edge else 1
+
+
+def _fd_too_short(name, op, n):  # edge is set
+    return ValueError(
+        f"pam: {name}: op {op} with edge needs an axis of at least "
+        f"{fd_min_rows(op, True)} samples, got {n}")
+
+
 def fd_apply(y, x, gf, gb, op: int, edge: bool, row0: int, nglob: int,
              rbegin: int, rend: int, coeff: float):
     """Stencil ``op`` along axis 0 of the [nloc, m] block ``x`` into rows
@@ -423,6 +438,8 @@ def fd_apply(y, x, gf, gb, op: int, edge: bool, row0: int, nglob: int,
     name = "pam_fd_apply"
     k, dt = _real_code(y)
     nloc, m = x.shape
+    if edge and nglob < _FD_EDGE_MIN.get(op, 1):
+        raise _fd_too_short(name, op, nglob)
     halo = (fd_halo_width(op), m)
     for t, shape in ((x, y.shape), (gf, halo), (gb, halo)):
         if t is not None and (t.dtype != y.dtype or t.shape != shape):
@@ -472,6 +489,8 @@ def fd_serial(y, x, op: int, edge: bool, coeff: float):
     k, dt = _real_code(y)
     batch, d, m = x.shape
     _shaped("pam_fd_serial", (batch, d, m), _dst("pam_fd_serial", y))
+    if edge and d < _FD_EDGE_MIN.get(op, 1):
+        raise _fd_too_short("pam_fd_serial", op, d)
     _run("pam_fd_serial", int(op), 1 if edge else 0, x.contiguous(), y,
          batch, d, k * m, float(coeff), dt)
 
